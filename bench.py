@@ -9,6 +9,10 @@ Workload (BASELINE.json configs[1]): B = 65 536 trajectories per GPU, horizon N 
 3->50->1, fp32. Weak scaling: every rank runs its own 65 536 trajectories.
 
 Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the roofline definitions.
+
+A plain run sets up, warms up, times the steps and prints the line. --full adds what takes runs of its own after
+the timed region: the grad check against the fp64 checker and the CPU baseline. --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -31,6 +35,7 @@ FP32_PEAK_TFLOPS = 157.3          # MI355X dense FP32 (vector = MFMA), MI355X_MI
 F16_PEAK_TFLOPS = 2500.0          # MI355X dense FP16/BF16 MFMA (no sparsity), MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0             # MI355X HBM3E spec
 ALPHA = 20.0                      # UL/Main.py:192
+DUMP_BUDGET_BYTES = 64 * 10**6    # --dump-outputs: all files together
 GRAD_CHECK_BUDGET_S = 300.0       # rank 0's post-timing check of its shard; the process group waits 30 min
 
 
@@ -296,6 +301,37 @@ def grad_check(sim, ctrl, X, S, N, dev, precision, B_check=None):
             "oracle": "oracle/rollout_torch.py fp64 on the GPU, chunked over trajectories (checker only)"}
 
 
+def step_outputs(ctrl, loss, feats, trajectory):
+    """What a caller of the timed step receives from it, cloned on the device: the loss, MPCLoss's per-trajectory
+    features and trajectory, the controller's gradients and its parameters after the optimizer step."""
+    out = {"loss": loss}
+    out.update({f"feat_{k}": v for k, v in feats.items()})
+    if trajectory is not None:
+        out["trajectory"] = trajectory
+    for n, p in ctrl.named_parameters():
+        if p.grad is not None:
+            out["grad_" + n.replace(".", "_")] = p.grad
+            out["param_" + n.replace(".", "_")] = p
+    return {k: v.detach().clone() for k, v in out.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy in float32, at most DUMP_BUDGET_BYTES in all. Smallest first, each array is written whole while it
+    fits an equal share of what is left of the budget; one above its share is written as a fixed, seeded sample of its
+    flattened elements (the same elements in every run of the same shapes)."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        a = t.float().cpu().numpy()
+        share = left // (len(todo) - i)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -304,10 +340,17 @@ def main():
     ap.add_argument("--batch", type=int, default=65536, help="trajectories per GPU")
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--hidden", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the grad check against the fp64 torch restatement and the "
+                         "CPU baseline (each a run of its own; a plain run prints the line without them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, features, trajectory, controller gradients "
+                         "and updated parameters) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--cpu-budget", type=float, default=24.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--grad-check", choices=("full", "off"), default="full",
-                    help="full: grad max-rel-err of the benchmarked batch vs the fp64 torch restatement (after timing)")
+                    help="with --full. full: grad max-rel-err of the benchmarked batch vs the fp64 torch restatement "
+                         "(after timing); off: leave it out")
     ap.add_argument("--precision", choices=("fp32", "f16"), default="fp32",
                     help="fp32: reference-accurate (default, config 2); f16: gate products in f16 in both passes, fp32 "
                          "accumulate (config 3)")
@@ -386,7 +429,7 @@ def main():
                 # carries the host round trip): ev[2] -> ev[3] is the step's exchange as the stream sees it
                 ev[3].record(stream)
         opt.step()
-        return loss
+        return loss, feats
 
     captured = None
     if args.graphed:
@@ -410,13 +453,18 @@ def main():
     t0 = time.perf_counter()
     for k in range(args.steps):
         if captured is not None:
-            loss = captured(X, S)[0]
+            loss, *feats = captured(X, S)
         else:
-            loss = step(marks[k])
+            loss, feats = step(marks[k])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        if captured is not None:   # captured_step's body returns (loss, cost, command, error, prediction)
+            feats = dict(zip(("loss", "command", "error", "prediction"), feats))
+        dumped = step_outputs(ctrl, loss, feats, loss_fn.last_trajectory)
     dt_local = dt
     if world > 1:
         t = torch.tensor([dt], device=dev)
@@ -516,7 +564,10 @@ def main():
             "hbm_roofline_frac": value / world / hbm_roof,
             "loss": float(loss.item()),
         }
-        if args.grad_check != "off":
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
+            dumped = None
+        if args.full and args.grad_check != "off":
             if keep_budget is not None:
                 torch.cuda.empty_cache()   # the kept windows' workspace back to the device for the checker's chunks
             t_gc = time.perf_counter()
@@ -528,7 +579,7 @@ def main():
             line["grad_max_rel_err"] = gc.pop("grad_max_rel_err")
             line["out_max_rel_err"] = gc.pop("out_max_rel_err")
             line["grad_check"] = gc
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the line's own workload at H > 52 (config 5); the H <= 52 lines share config 2's (per rollout-step)
             line["cpu_baseline"] = cpu_baseline(args.cpu_budget, N=N if H > 52 else 10, H=H if H > 52 else 50)
         print(json.dumps(line), flush=True)

@@ -8,7 +8,7 @@ TAG=${1:-round2}
 O=$R/gpurun_out/cfg_$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 timeout -k 10 300 $B --batch 262144 --precision f16 --steps 10 --warmup 3 > $O/c3_f16.log 2>&1
 timeout -k 10 300 $B --batch 262144 --steps 10 --warmup 3 > $O/c3_fp32.log 2>&1
 timeout -k 10 300 $B --batch 15 --steps 50 --warmup 5 > $O/c1_b15.log 2>&1

@@ -12,5 +12,5 @@ else
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -rP > $OUT/pytest.log 2>&1
 fi
 tail -3 $OUT/pytest.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1
 tail -c 3000 $OUT/bench.log

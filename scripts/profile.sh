@@ -27,7 +27,7 @@ if [ "${3:-}" = gputest ]; then
   tail -1 $O/gputest.log
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 python3 $R/bench.py $ARGS --steps $K --warmup $W > $O/bench.log 2>&1
+timeout -k 10 600 python3 $R/bench.py --full $ARGS --steps $K --warmup $W > $O/bench.log 2>&1
 grep '^{' $O/bench.log | tail -c 400
 QUIET="--no-cpu-baseline --grad-check off"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o $TAG -- python3 $R/bench.py $ARGS --steps $KS --warmup $W $QUIET > $O/trace.log 2>&1
