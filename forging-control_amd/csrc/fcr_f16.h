@@ -484,8 +484,5 @@ __device__ __forceinline__ void pack_fwd16_item(const PackArgs &a, int l, _Float
     dst[((size_t)rk * kWave + lane) * 8 + j] = hi;
     dst[((nq + (size_t)r * KL + kb) * kWave + lane) * 8 + j] = lo;
 }
-__global__ void pack_fwd16_kernel(PackArgs a, int l, _Float16 *dst) {
-    pack_fwd16_item(a, l, dst, blockIdx.x * blockDim.x + threadIdx.x);
-}
 
 }  // namespace fcr

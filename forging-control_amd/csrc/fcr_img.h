@@ -117,9 +117,6 @@ __device__ __forceinline__ void pack_img_item(const PackArgs &a, int l, _Float16
     dst[off] = hi;
     dst[(size_t)HS * TU * 4 + off] = lo;
 }
-__global__ void pack_img_kernel(PackArgs a, int l, _Float16 *dst) {
-    pack_img_item(a, l, dst, blockIdx.x * blockDim.x + threadIdx.x);
-}
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;

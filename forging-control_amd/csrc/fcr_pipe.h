@@ -55,7 +55,7 @@ struct PipeArgs {
     float *loss;       // forward: the batch mean (the last group to finish reduces the per-group sums)
 };
 
-// The counters are zeroed by each forward call's pack_all_kernel (fcr_abi.hip), ahead of the forward and its backward
+// The counters are zeroed by each forward call's pack_all_kernel (fcr_rollout.hip), ahead of the forward and its backward
 // on the call's stream, by a kernel rather than hipMemsetAsync: a memset captured into a HIP graph left stale counters
 // in replays (the consumers ran ahead on the previous replay's rows: profiles/round6_b15_pipe_graph.log); a kernel node
 // has the ordering and the release / acquire of any kernel boundary. A backward leaves its own counters zeroed (the

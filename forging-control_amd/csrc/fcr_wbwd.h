@@ -60,7 +60,7 @@ struct WbGeo {
 };
 // 256 columns x 128 trajectories, 4 + 4 waves (round 4): every layer; two column blocks at Hp = 256 form the same dgates
 using WbG256 = WbGeo<256, 128, 4, 4>;
-// 256 columns x 256 trajectories, 4 + 8 waves (layers >= 1 at B >= 32 768, fcr_abi.hip launch_fb): A staged once per 256
+// 256 columns x 256 trajectories, 4 + 8 waves (layers >= 1 at B >= 32 768, fcr_wide.hip launch_fb): A staged once per 256
 // trajectories (half the A bytes per trajectory of WbG256); each producer thread forms the dgates of two rows, each
 // consumer 32 columns x 256 trajectories; 168 registers per wave (12 waves), 129 KB of LDS
 using WbG256w = WbGeo<256, 256, 8, 4>;

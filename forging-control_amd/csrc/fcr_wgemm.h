@@ -1,7 +1,7 @@
 // fcr_wgemm.h — H > 52 (config 5): one LSTM cell of the whole batch as ONE hand-written split-f16 MFMA GEMM
 // with the cell update in its epilogue. Every layer, every H: the host pads H to Hp, a multiple of 64, with
 // zero-weight units (their gates stay i = f = o = 1/2, g = 0, so c = h = 0 and they add nothing to any product: the
-// same padding the H <= 52 tiers use, fcr_abi.hip slot_tier).
+// same padding the H <= 52 tiers use, fcr_host.h slot_tier).
 //
 // Product: G[b][r] = sum_k x[b][k] W[r][k] over the cell's two inputs, fp32-accurate from f16 halves
 //   G = W_hi x_hi + W_hi x_lo + W_lo x_hi          (three MFMAs per 32-k block; the dropped lo.lo <= 2^-22)

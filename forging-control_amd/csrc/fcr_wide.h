@@ -4,9 +4,9 @@
 // runs batch-wide: the gate GEMM with the cell update in its epilogue (fcr_wgemm.h), the backward cell as one fused
 // kernel (fcr_wbwd.h); everything around them — window rows, controller, readout, costs, their backward — is here,
 // one thread per trajectory (or a few lanes per trajectory), batch-major so every access is coalesced. All of it runs
-// at Hp, H padded to whole 64-unit blocks with zero-weight units (fcr_abi.hip wide_hp).
+// at Hp, H padded to whole 64-unit blocks with zero-weight units (fcr_wide.hip wide_hp).
 //
-// Data (fcr_abi.hip WideLayout), row-major with the batch index outermost inside a slice:
+// Data (fcr_wide.hip WideLayout), row-major with the batch index outermost inside a slice:
 //   WR  [10][B][64] halves   layer-0 window records [hi | lo] of the current window (Functions.py:1395-1396, 1433-1434)
 //   HR  [2][10][B][2Hp]      h records [hi | lo] of two layers' cells (layer l in slot l & 1)
 //   Cs  [3][10][Hp/8][B][8]  c_t of every cell of the current window (k8 rows, below)

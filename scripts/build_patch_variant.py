@@ -2,6 +2,7 @@
 scripts/kbench.py; the product sources are never touched). usage:
     python scripts/build_patch_variant.py NAME PATCHES.json [extra hipcc flags...]
 PATCHES.json: [[file relative to csrc, old text, new text], ...]; every old text must occur exactly once."""
+import glob
 import json
 import os
 import shutil
@@ -21,8 +22,8 @@ for f, old, new in json.load(open(spec)):
     open(p, "w").write(s.replace(old, new))
 os.makedirs(os.path.join(ROOT, "lib_ab"), exist_ok=True)
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC",
-       "-I", os.path.join(ROOT, "include"), "-I", src, *sys.argv[3:], os.path.join(src, "fcr_abi.hip"),
-       os.path.join(src, "fcr_rows.hip"), "-o", os.path.join(ROOT, "lib_ab", name + ".so")]
+       "-I", os.path.join(ROOT, "include"), "-I", src, *sys.argv[3:], *sorted(glob.glob(os.path.join(src, "*.hip"))),
+       "-o", os.path.join(ROOT, "lib_ab", name + ".so")]
 subprocess.check_call(cmd)
 shutil.rmtree(tmp)
 print("built lib_ab/%s.so" % name)

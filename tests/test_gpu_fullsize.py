@@ -185,7 +185,7 @@ def test_config5_full_batch(seed):
 @pytest.mark.parametrize("B", [32768, 32767])
 def test_wide_backward_geometries_at_their_batch_threshold(B):
     """The wide backward's layers >= 1 run 256 x 256-trajectory workgroups from B = 32 768 on and 256 x 128 below
-    (fcr_abi.hip launch_fb): both sides of the threshold at H = 264 (Hp = 320: three 256-column blocks, three row-bound
+    (fcr_wide.hip launch_fb): both sides of the threshold at H = 264 (Hp = 320: three 256-column blocks, three row-bound
     slots) and N = 2, every trajectory against the fp64 oracle."""
     p = synth_params(264, 7)
     params = {"Wih": [np.asarray(a, np.float64) for a in p["Wih"]], "Whh": [np.asarray(a, np.float64) for a in p["Whh"]],
