@@ -19,8 +19,8 @@ _IN_TREE = os.path.join(_HERE, "lib", _LIB_NAME)
 LIB_PATH = os.environ.get("FCR_LIB") or _IN_TREE
 
 FCR_OK = 0
-# 6 (round 6): kept wide windows store gate activations (not pre-activations), fcr_wide_bwd_cell[_workspace] exported
-ABI_VERSION = 6
+# 7: fcr_closed_loop gains process_noise / meas_noise (NULL = none), fcr_lstm_rollout[_workspace_size] exported
+ABI_VERSION = 7
 PRECISION_FP32, PRECISION_F16 = 0, 1
 ERRORS = {-1: "FCR_EINVAL", -2: "FCR_EWORKSPACE", -3: "FCR_EHIP", -4: "FCR_EUNSUPPORTED"}
 
@@ -30,7 +30,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_fnn_workspace_size", "fcr_fnn_forward", "fcr_fnn_backward", "fcr_set_small_batch_limit",
            "fcr_get_small_batch_limit", "fcr_set_small_pipe_limit", "fcr_get_small_pipe_limit", "fcr_set_small_pipe_sets",
            "fcr_get_small_pipe_sets", "fcr_set_wide_keep_budget", "fcr_get_wide_keep_budget", "fcr_last_error",
-           "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell")
+           "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
+           "fcr_lstm_rollout")
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
 
@@ -86,6 +87,7 @@ class FcrClosedLoop(ctypes.Structure):
         ("ctrl_hidden", ctypes.c_int32), ("in_scale", ctypes.c_double * 2),
         ("ref_scale", ctypes.c_double), ("out_scale", ctypes.c_double),
         ("x", ctypes.c_void_p), ("u", ctypes.c_void_p),
+        ("process_noise", ctypes.c_void_p), ("meas_noise", ctypes.c_void_p),   # (B,T,5) fp64 each, or NULL
     ]
 
 
@@ -133,6 +135,11 @@ def load() -> ctypes.CDLL:
         lib.fcr_lstm_backward.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(FcrWeights), vp,
                                           ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, sz, vp]
         lib.fcr_lstm_backward.restype = i32
+        lib.fcr_lstm_rollout_workspace_size.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(sz)]
+        lib.fcr_lstm_rollout_workspace_size.restype = i32
+        lib.fcr_lstm_rollout.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(FcrWeights), vp, vp,
+                                         ctypes.POINTER(ctypes.c_float), vp, vp, vp, sz, vp]
+        lib.fcr_lstm_rollout.restype = i32
         lib.fcr_closed_loop_run.argtypes = [ctypes.POINTER(FcrClosedLoop), vp]
         lib.fcr_closed_loop_run.restype = i32
         lib.fcr_window_gather.argtypes = [ctypes.POINTER(FcrWindows), i32, vp, vp, vp, vp, vp, vp]

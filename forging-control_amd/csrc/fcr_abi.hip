@@ -110,6 +110,23 @@ int check_lstm_dims(const fcr_dims *d) {
     return FCR_OK;
 }
 
+// fcr_lstm_rollout: the fcr_lstm_* convention with N = T steps; B = 0 is a no-op, so it passes
+int check_lro_dims(const fcr_dims *d) {
+    if (!d) return fail(FCR_EINVAL, "dims is NULL");
+    if (d->B < 0) return fail(FCR_EINVAL, "B=%d must be >= 0", d->B);
+    if (d->N < 1) return fail(FCR_EINVAL, "N=%d (the steps T) must be >= 1", d->N);
+    if (d->L != kL) return fail(FCR_EUNSUPPORTED, "L=%d: the window is fixed at 10 rows", d->L);
+    if (d->layers != kLayers) return fail(FCR_EUNSUPPORTED, "layers=%d: built for 3", d->layers);
+    if (d->in_dim != kIn || d->out_dim != kOut)
+        return fail(FCR_EUNSUPPORTED, "in/out = %d/%d: built for 5/4", d->in_dim, d->out_dim);
+    if (d->H < 1 || is_wide(d))
+        return fail(FCR_EUNSUPPORTED, "H=%d: the surrogate rollout is built for 1..%d (the fused cells)", d->H, 4 * kMaxSlots);
+    if (d->precision != FCR_PRECISION_FP32)
+        return fail(FCR_EUNSUPPORTED, "precision=%d: the surrogate rollout runs FCR_PRECISION_FP32 (0) only", d->precision);
+    if ((long long)d->B * d->N > (1LL << 31)) return fail(FCR_EINVAL, "B*N too large");
+    return FCR_OK;
+}
+
 int lstm_weights_ok(const fcr_weights *w) {
     if (!w || !w->fc_w || !w->fc_b) return 0;
     for (int l = 0; l < kLayers; ++l)
@@ -279,6 +296,25 @@ int fcr_lstm_backward(const fcr_dims *d, const fcr_weights *w, const float *dy, 
     if ((rc = check_ws("fcr_lstm_backward", ws, ws_bytes, need))) return rc;
     if (!is_wide(d)) return sur_backward(d, dy, g_w_ih, g_w_hh, g_fc_w, g_fc_b, g_x, (char *)ws, (hipStream_t)stream);
     return surw_backward(d, w, dy, g_w_ih, g_w_hh, g_fc_w, g_fc_b, g_x, (char *)ws, (hipStream_t)stream);
+}
+
+int fcr_lstm_rollout_workspace_size(const fcr_dims *dims, size_t *bytes) {
+    int rc = check_lro_dims(dims);
+    if (rc) return rc;
+    if (!bytes) return fail(FCR_EINVAL, "bytes is NULL");
+    *bytes = lro_workspace(dims);
+    return FCR_OK;
+}
+
+int fcr_lstm_rollout(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
+                     const float *noise, float *xhat, void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_lro_dims(d);
+    if (rc) return rc;
+    if (d->B == 0) return FCR_OK;
+    if (!window0 || !cmd || !xhat || !ws) return fail(FCR_EINVAL, "fcr_lstm_rollout: a required pointer is NULL");
+    if (!lstm_weights_ok(w)) return fail(FCR_EINVAL, "fcr_lstm_rollout: an LSTM/fc weight pointer is NULL");
+    if ((rc = check_ws("fcr_lstm_rollout", ws, ws_bytes, lro_workspace(d)))) return rc;
+    return lro_forward(d, w, window0, cmd, gain, noise, xhat, (char *)ws, (hipStream_t)stream);
 }
 
 int fcr_fnn_workspace_size(int32_t B, int32_t hidden, size_t *bytes) {

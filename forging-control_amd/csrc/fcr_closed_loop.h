@@ -10,7 +10,8 @@
 //
 // One lane owns one trajectory: fp64 state in VGPRs for all T steps, the 3->H->1 controller in fp32 as
 // torch evaluates it (weights in LDS, one FMA chain per hidden unit), the plant in fp64. HBM sees the
-// reference (8 B) in and u (8 B) + the state (40 B) out per step.
+// reference (8 B) in and u (8 B) + the state (40 B) out per step; with pre-drawn process and measurement noise
+// (closed_loop_noise_kernel) 40 B or 80 B more in.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,6 +71,66 @@ __global__ __launch_bounds__(kClBlock) void closed_loop_kernel(ClArgs a) {
         o += 5;
 #pragma unroll
         for (int i = 0; i < 5; ++i) o[i] = x[i];
+    }
+}
+
+// The same loop under the harness's pre-drawn noise, a kernel of its own so the one above keeps its code: process
+// noise wn (B,T,5), added to the right-hand side at every RK4 stage of step t (fcr_plant.h), and measurement noise
+// vn (B,T,5), added to the RECORD x[:, t+1] only — the controller reads the record at step t+1 (the harness feeds
+// make_step's return value back in, Functions.py:1178-1183) while the integration continues from the unperturbed
+// state. Either may be null. Out of scope: the smooth model measures p_eff, not p (template_model.py:154-155); the
+// record here is p + v.
+template <bool SMOOTH>
+__global__ __launch_bounds__(kClBlock) void closed_loop_noise_kernel(ClArgs a, const double *wn, const double *vn) {
+    __shared__ float w[kClMaxHidden * 5];        // [j] = (w_inp[j][0..2], b_inp[j], w_out[j])
+    for (int i = threadIdx.x; i < a.hidden; i += kClBlock) {
+        w[i * 5 + 0] = a.w_inp[i * 3 + 0];
+        w[i * 5 + 1] = a.w_inp[i * 3 + 1];
+        w[i * 5 + 2] = a.w_inp[i * 3 + 2];
+        w[i * 5 + 3] = a.b_inp[i];
+        w[i * 5 + 4] = a.w_out[i];
+    }
+    __syncthreads();
+    const int b = blockIdx.x * kClBlock + threadIdx.x;
+    if (b >= a.B) return;
+    double x[5];
+    double *o = a.x + (size_t)b * (a.T + 1) * 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        x[i] = a.x0[(size_t)b * 5 + i];
+        o[i] = x[i];
+    }
+    const double *rb = a.ref + (size_t)b * a.T;
+    double *ub = a.u + (size_t)b * a.T;
+    double m1 = x[1], m4 = x[4];                  // what the controller reads: the recorded y_dot and z
+    for (int t = 0; t < a.T; ++t) {
+        const float s0 = (float)(m1 / a.in_scale0), s1 = (float)(m4 / a.in_scale1), s2 = (float)(rb[t] / a.ref_scale);
+        float v = 0.0f;
+        for (int j = 0; j < a.hidden; ++j) {
+            const float *wj = w + j * 5;
+            float z = fmaf(wj[2], s2, fmaf(wj[1], s1, fmaf(wj[0], s0, wj[3])));
+            z = z > 0.0f ? z : 0.0f;
+            v = fmaf(wj[4], z, v);
+        }
+        v = fminf(fmaxf(v, -1.0f), 1.0f);
+        const double u = (double)(v * (float)a.out_scale);
+        ub[t] = u;
+        double wt[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, vt[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        const size_t nt = ((size_t)b * a.T + t) * 5;
+        if (wn) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) wt[i] = wn[nt + i];
+        }
+        if (vn) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) vt[i] = vn[nt + i];
+        }
+        plant::rk4_step<SMOOTH>(x, u, a.dt, a.substeps, wt);
+        o += 5;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) o[i] = x[i] + vt[i];
+        m1 = x[1] + vt[1];
+        m4 = x[4] + vt[4];
     }
 }
 

@@ -118,4 +118,9 @@ int sur_forward(const fcr_dims *d, const fcr_weights *w, const float *x, float *
 int sur_backward(const fcr_dims *d, const float *dy, float *const *g_w_ih, float *const *g_w_hh, float *g_fc_w,
                  float *g_fc_b, float *g_x, char *base, hipStream_t s);
 
+// the H <= 52 surrogate's command-driven rollout (fcr_lstm_rollout.h); gain: host float[4] or null (= 1)
+size_t lro_workspace(const fcr_dims *d);
+int lro_forward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
+                const float *noise, float *xhat, char *base, hipStream_t s);
+
 }  // namespace fcr

@@ -24,6 +24,8 @@ struct PackArgs {
 // the generated rows x̂ = fc(h) + b + noise (|h| < 1), sum_k |fc.W[c,k]| + |fc.b[c]|; u is in [-1, 1].
 // With s_c = 0 (every input the reference's MaxAbs scalers produce) the rollout is bit-identical to the
 // unguarded one. Values whose scaled weights leave the f16 range (|v W| ~ 1e9 and beyond) are not covered.
+// (The surrogate's command-driven rollout bounds its columns itself — an unbounded command column, a gain on the
+// generated rows — and balances s_c against the size of W_ih0[:, c]: fcr_lstm_rollout.h.)
 constexpr int kRangeBlocks = 128;
 constexpr int kRangeThreads = 256;
 // wsc[c] = 2^-s_c (c < 5; wsc[5..7] = 1) from the partial maxima and the readout's bound (see above)

@@ -98,6 +98,38 @@ __device__ __forceinline__ void rk4_step(double (&x)[5], double u, double dt, in
     }
 }
 
+// The same step under process noise w in the units of xdot: do-mpc adds the w of a `process_noise=True` state to its
+// right-hand side (template_model.py:145-149) and the harness holds one draw over the whole sampling step
+// (Functions.py:1176-1183), so EVERY stage of every sub-step evaluates k = f(x, u) + w (not x + TS·w after the step).
+// w is constant over the step, so its share of each stage state and of the update is a term of its own —
+// x + c (f + w) = (x + c f) + c w, and dt/6 (6 w) = dt w — added AFTER the expressions of the noise-free step: with
+// w = 0 every one of them, however the compiler contracts it, is followed by + 0, and the step is the one above bit
+// for bit. An overload, so the noise-free callers keep their code.
+template <bool SMOOTH>
+__device__ __forceinline__ void rk4_step(double (&x)[5], double u, double dt, int substeps, const double (&w)[5]) {
+    double hw[5], dw[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        hw[i] = dt / 2 * w[i];
+        dw[i] = dt * w[i];
+    }
+    for (int m = 0; m < substeps; ++m) {
+        double k1[5], k2[5], k3[5], k4[5], xs[5];
+        forging_rhs<SMOOTH>(x, u, k1);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt / 2 * k1[i]) + hw[i];
+        forging_rhs<SMOOTH>(xs, u, k2);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt / 2 * k2[i]) + hw[i];
+        forging_rhs<SMOOTH>(xs, u, k3);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt * k3[i]) + dw[i];
+        forging_rhs<SMOOTH>(xs, u, k4);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) x[i] = (x[i] + dt / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i])) + dw[i];
+    }
+}
+
 constexpr int kPlantBlock = 256;
 
 // x (B, S+1, 5): x[b, 0] = x0[b], x[b, t+1] = F(x[b, t], u[b, t]) for u (B, S)

@@ -1,7 +1,8 @@
 // fcr_rollout.hip — host side of the H <= 52 engines: the rollout (the fused kernels, the small-batch and the
 // layer-pipelined families: fcr_fwd.h, fcr_bwd.h, fcr_small.h, fcr_pipe.h) and the surrogate training step on the same
-// cells (fcr_sur.h); and the kernels every engine shares (fcr_shared_kernels.h, pack_all_kernel) behind the launchers
-// fcr_host.h declares. The C ABI in fcr_abi.hip calls in through fcr_host.h.
+// cells (fcr_sur.h) and its command-driven free run (fcr_lstm_rollout.h); and the kernels every engine shares
+// (fcr_shared_kernels.h, pack_all_kernel) behind the launchers fcr_host.h declares. The C ABI in fcr_abi.hip calls in
+// through fcr_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -18,6 +19,7 @@
 #include "fcr_shared_kernels.h"
 #include "fcr_small.h"
 #include "fcr_sur.h"
+#include "fcr_lstm_rollout.h"   // after the others: built from fcr_fwd.h's parts
 
 namespace fcr {
 namespace {
@@ -612,6 +614,78 @@ int sur_backward(const fcr_dims *d, const float *dy, float *const *g_w_ih, float
     hipLaunchKernelGGL(sur_fc_final_kernel, dim3(kOut * d->H + kOut), dim3(256), 0, s, (const float *)part, nfb, d->H, g_fc_w,
                        g_fc_b);
     return launch_check("sur_fc_final_kernel");
+}
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// Command-driven surrogate rollout (fcr_lstm_rollout.h). Workspace: the packed forward fragments and readout as the
+// rollout packs them, the range guard's partials and layer 1's h slab of ONE window per wave — nothing scales with T.
+struct LroLayout : PackedLayout {
+    int nw, nw_pad;
+    size_t rpart, hseq, total;
+};
+LroLayout make_lro(const fcr_dims *d) {
+    LroLayout L{};
+    L.HS = slot_tier(d->H);
+    L.nw = (d->B + kTile - 1) / kTile;
+    L.nw_pad = (L.nw + kFwdWaves - 1) / kFwdWaves * kFwdWaves;
+    Arena take;
+    take_packed(take, L, false);
+    L.rpart = take(sizeof(float) * kLroPart * kRangeBlocks);
+    L.hseq = take(sizeof(f32x4) * (size_t)L.nw_pad * kL * L.HS * 16);   // Geo<HS>::QC per cell
+    L.total = take.off;
+    return L;
+}
+
+template <int HS>
+int launch_lro_t(const LroArgs &a, const LroLayout &L, hipStream_t s) {
+    constexpr int lds = LroGeo<HS>::LDS;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (const int rc = lds_attr((const void *)fcr_lstm_rollout_kernel<HS>, lds, attr_done, "lstm_rollout")) return rc;
+    hipLaunchKernelGGL((fcr_lstm_rollout_kernel<HS>), dim3(L.nw_pad / kFwdWaves), dim3(kFwdWaves * kWave), lds, s, a);
+    return launch_check("fcr_lstm_rollout_kernel");
+}
+
+}  // namespace
+
+size_t lro_workspace(const fcr_dims *d) { return make_lro(d).total; }
+
+int lro_forward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
+                const float *noise, float *xhat, char *base, hipStream_t s) {
+    const LroLayout L = make_lro(d);
+    int rc;
+    LroArgs a{};
+    a.B = d->B;
+    a.T = d->N;
+    a.window0 = window0;
+    a.cmd = cmd;
+    a.noise = noise;
+    a.g0 = gain ? gain[0] : 1.0f;
+    a.g1 = gain ? gain[1] : 1.0f;
+    a.g2 = gain ? gain[2] : 1.0f;
+    a.g3 = gain ? gain[3] : 1.0f;
+    a.xhat = xhat;
+    a.hseq = (f32x4 *)(base + L.hseq);
+    a.p = packed_ptrs(L, base);
+    // range guard of the window columns from everything this rollout can put into them (fcr_lstm_rollout.h)
+    float *part = (float *)(base + L.rpart), *wsc = (float *)(base + L.wsc);
+    const size_t rows = (size_t)d->B * (d->N > kL ? d->N : kL);
+    const LroRangeArgs rg{a.g0, a.g1, a.g2, a.g3, w->fc_w, w->fc_b, w->w_ih[0], d->H, wsc};
+    const bool one = rows <= 16 * kRangeThreads;   // small batch: one block, the final step inside (one launch)
+    hipLaunchKernelGGL(lro_range_partial_kernel, dim3(one ? 1 : kRangeBlocks), dim3(kRangeThreads), 0, s, window0, cmd,
+                       noise, d->B, d->N, part, one ? 1 : 0, rg);
+    if ((rc = launch_check("lro_range_partial_kernel"))) return rc;
+    if (!one) {
+        hipLaunchKernelGGL(lro_range_final_kernel, dim3(1), dim3(64), 0, s, (const float *)part, kRangeBlocks, rg);
+        if ((rc = launch_check("lro_range_final_kernel"))) return rc;
+    }
+    if ((rc = launch_pack_all(w, d->H, 0, L, false, base, nullptr, 0, s))) return rc;
+    switch (L.HS) {
+        case 4: return launch_lro_t<4>(a, L, s);
+        case 8: return launch_lro_t<8>(a, L, s);
+        default: return launch_lro_t<13>(a, L, s);
+    }
 }
 
 }  // namespace fcr

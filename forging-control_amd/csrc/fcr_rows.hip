@@ -77,11 +77,21 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
         return fail(FCR_EINVAL, "fcr_closed_loop_run: a required pointer is NULL");
     if ((((uintptr_t)c->x0) | ((uintptr_t)c->ref) | ((uintptr_t)c->x) | ((uintptr_t)c->u)) & 7)
         return fail(FCR_EINVAL, "fcr_closed_loop_run: fp64 buffers must be 8-byte aligned");
-    closed_loop::ClArgs a{c->B, c->T, c->substeps, c->ctrl_hidden, c->ts / c->substeps, c->x0, c->ref,
+    if ((((uintptr_t)c->process_noise) | ((uintptr_t)c->meas_noise)) & 7)
+        return fail(FCR_EINVAL, "fcr_closed_loop_run: noise buffers must be 8-byte aligned (fp64)");    closed_loop::ClArgs a{c->B, c->T, c->substeps, c->ctrl_hidden, c->ts / c->substeps, c->x0, c->ref,
                           c->ctrl_w_inp, c->ctrl_b_inp, c->ctrl_w_out, c->in_scale[0], c->in_scale[1],
                           c->ref_scale, c->out_scale, c->x, c->u};
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((c->B + closed_loop::kClBlock - 1) / closed_loop::kClBlock);
+    if (c->T > 0 && (c->process_noise || c->meas_noise)) {   // the harness's noise: a kernel of its own
+        if (c->smooth)
+            hipLaunchKernelGGL(closed_loop::closed_loop_noise_kernel<true>, grid, dim3(closed_loop::kClBlock), 0, s, a,
+                               c->process_noise, c->meas_noise);
+        else
+            hipLaunchKernelGGL(closed_loop::closed_loop_noise_kernel<false>, grid, dim3(closed_loop::kClBlock), 0, s, a,
+                               c->process_noise, c->meas_noise);
+        return launch_check("closed_loop_noise_kernel");
+    }
     if (c->smooth)
         hipLaunchKernelGGL(closed_loop::closed_loop_kernel<true>, grid, dim3(closed_loop::kClBlock), 0, s, a);
     else

@@ -9,11 +9,14 @@ of trajectories; the controller is the 3->50->1 FNN.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
+from . import _native
 from .functions import _simulator_params
-from .rollout import WINDOW_ROWS, rollout
+from .rollout import WINDOW_ROWS, _ptr, _stream, make_dims, rollout
 
 
 def simulate_step(simulator, windows: torch.Tensor, noise: torch.Tensor | None = None) -> torch.Tensor:
@@ -30,6 +33,76 @@ def simulate_step(simulator, windows: torch.Tensor, noise: torch.Tensor | None =
                       tuple(_to(p, dev) for p in _flat(_simulator_params(simulator))), 1, 0.0,
                       None if noise is None else noise.to(**f32).reshape(B, 1, 4))
     return out[5][:, 0, :]
+
+
+def simulate_rollout(simulator, window0: torch.Tensor, cmd: torch.Tensor, gain=None,
+                     noise: torch.Tensor | None = None) -> torch.Tensor:
+    """The surrogate free-running for T steps on its own predictions and a given command sequence — the
+    ``results_LSTM`` track of ``NeuralNetwork.loop`` (Functions.py:1196-1231) — for a batch, in scaled units.
+
+    ``window0`` (B,10,5) and ``cmd`` (B,T) on a ROCm device; ``gain``: 4 host numbers (None = 1), what the harness's
+    ``scalers['output'].inverse_transform`` then ``scalers['input'].transform`` amount to between steps
+    (out_scale / in_scale[:4]); ``noise`` (B,T,4) or None. Step 0 runs ``window0`` with its last row's command
+    replaced by ``cmd[:,0]``; step t >= 1 drops the oldest row and appends ``[gain * x̂_{t-1}, cmd[:,t]]``;
+    ``x̂_t = LSTM(window_t) + noise[:,t]``. Returns x̂ (B,T,4).
+
+    H <= 52 runs all T steps in ONE launch (``fcr_lstm_rollout``, csrc/fcr_lstm_rollout.h); a wider surrogate
+    composes T calls of :func:`simulate_step` with the window update in torch."""
+    if window0.dim() != 3 or window0.shape[1:] != (WINDOW_ROWS, 5):
+        raise ValueError(f"window0 must be (B, 10, 5), got {tuple(window0.shape)}")
+    B, dev = window0.shape[0], window0.device
+    if cmd.dim() != 2 or cmd.shape[0] != B or cmd.shape[1] < 1:
+        raise ValueError(f"cmd must be (B, T) with T >= 1 and B = {B}, got {tuple(cmd.shape)}")
+    T = cmd.shape[1]
+    if noise is not None and tuple(noise.shape) != (B, T, 4):
+        raise ValueError(f"noise must be (B, T, 4) = {(B, T, 4)}, got {tuple(noise.shape)}")
+    g = np.ones(4, np.float32) if gain is None else np.asarray(gain, np.float32).reshape(-1)
+    if g.shape != (4,):
+        raise ValueError(f"gain must hold 4 numbers, got {g.shape[0]}")
+    if dev.type != "cuda":
+        raise RuntimeError(f"simulate_rollout runs on a ROCm device only (window0 on {dev})")
+    for name, t in (("cmd", cmd), ("noise", noise)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} must be on {dev}, found it on {t.device}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    w_ih, w_hh, fc_w, fc_b = _flat(_simulator_params(simulator))
+    H = w_hh[0].shape[1]
+    with torch.no_grad():
+        w = window0.to(**f32).contiguous()
+        c = cmd.to(**f32).contiguous()
+        nz = None if noise is None else noise.to(**f32).contiguous()
+        if H > 52:
+            return _rollout_by_steps(simulator, w, c, torch.as_tensor(g, device=dev), nz)
+        keep = [t.detach().to(**f32).contiguous() for t in list(w_ih) + list(w_hh) + [fc_w, fc_b]]
+        fw = _native.FcrWeights()
+        for l in range(3):
+            fw.w_ih[l], fw.w_hh[l] = keep[l].data_ptr(), keep[3 + l].data_ptr()
+        fw.fc_w, fw.fc_b = keep[6].data_ptr(), keep[7].data_ptr()
+        dims = make_dims(B, T, H, 3, 1, 0.0)
+        lib = _native.load()
+        nbytes = ctypes.c_size_t(0)
+        _native.check(lib.fcr_lstm_rollout_workspace_size(ctypes.byref(dims), ctypes.byref(nbytes)),
+                      "fcr_lstm_rollout_workspace_size")
+        ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+        xhat = torch.empty(B, T, 4, **f32)
+        _native.check(lib.fcr_lstm_rollout(ctypes.byref(dims), ctypes.byref(fw), _ptr(w), _ptr(c),
+                                           (ctypes.c_float * 4)(*g.tolist()), _ptr(nz), _ptr(xhat), _ptr(ws),
+                                           ws.numel(), _stream(dev)), "fcr_lstm_rollout")
+    return xhat
+
+
+def _rollout_by_steps(simulator, window0, cmd, gain, noise):
+    """simulate_rollout as T launches of simulate_step with the window shuffled in torch between them."""
+    B, T = cmd.shape
+    win = window0.clone()
+    win[:, WINDOW_ROWS - 1, 4] = cmd[:, 0]
+    out = torch.empty(B, T, 4, dtype=torch.float32, device=window0.device)
+    for t in range(T):
+        if t > 0:
+            row = torch.cat([gain * out[:, t - 1], cmd[:, t:t + 1]], dim=1)
+            win = torch.cat([win[:, 1:], row[:, None, :]], dim=1)
+        out[:, t] = simulate_step(simulator, win, None if noise is None else noise[:, t])
+    return out
 
 
 def controller_step(controller, X: torch.Tensor) -> torch.Tensor:

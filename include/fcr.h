@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FCR_ABI_VERSION 6   /* 6: kept wide windows hold gate activations; fcr_wide_bwd_cell */
+#define FCR_ABI_VERSION 7   /* 7: fcr_closed_loop gains process_noise / meas_noise; fcr_lstm_rollout */
 
 enum {
     FCR_OK = 0,
@@ -57,7 +57,8 @@ typedef struct fcr_dims {
     int32_t precision;   /* FCR_PRECISION_FP32 (0) or FCR_PRECISION_F16 (1), below */
 } fcr_dims;
 
-/* Arithmetic of the gate products (fcr_forward/fcr_backward; fcr_lstm_* ignore it and run fp32):
+/* Arithmetic of the gate products (fcr_forward/fcr_backward; fcr_lstm_forward/_backward ignore it and run fp32,
+ * fcr_lstm_rollout accepts FCR_PRECISION_FP32 only):
  *   FCR_PRECISION_FP32 — fp32-accurate: each operand split into two f16 halves, three f16 MFMAs per
  *                        product, fp32 accumulate (results within 1e-5 of an fp64 evaluation);
  *   FCR_PRECISION_F16  — config 3's reduced-precision mode ("bf16 storage/MFMA fwd"):
@@ -184,6 +185,14 @@ int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smo
  *   caller); controller weights as fcr_weights; in_scale = scalers['input'].scale_[0:2] (y_dot, z),
  *   ref_scale = scalers['y_dot'].scale_, out_scale = scalers['output'].scale_ (UL/Main.py:237-256);
  *   outputs x (B,T+1,5) with x[:,0] = x0 and u (B,T) the commands applied. fp64 buffers, fp32 weights.
+ * Optional pre-drawn noise of the harness (ABI v7; NULL = none, so a zero-initialised struct runs the noise-free
+ * loop, bit for bit as before):
+ *   process_noise (B,T,5) fp64, in the units of x_dot: do-mpc adds it to the right-hand side (template_model.py:
+ *     145-149) and the harness holds it over the sampling step (Functions.py:1176-1183), so every RK4 stage of
+ *     step t evaluates f(x,u) + process_noise[b,t];
+ *   meas_noise (B,T,5) fp64: x[:,t+1] records x_{t+1} + meas_noise[b,t], the controller reads that record at
+ *     step t+1, and the integration continues from the unperturbed state. (The smooth model measures p_eff, not p,
+ *     template_model.py:154-155; here the record is p + v.)
  */
 typedef struct fcr_closed_loop {
     int32_t B, T;
@@ -195,6 +204,7 @@ typedef struct fcr_closed_loop {
     double in_scale[2];
     double ref_scale, out_scale;
     double *x, *u;
+    const double *process_noise, *meas_noise; /* (B,T,5) each, or NULL (ABI v7) */
 } fcr_closed_loop;
 
 int fcr_closed_loop_run(const fcr_closed_loop *args, void *stream);
@@ -246,6 +256,23 @@ int fcr_lstm_forward(const fcr_dims *dims, const fcr_weights *w, const float *x,
 int fcr_lstm_backward(const fcr_dims *dims, const fcr_weights *w, const float *dy,
                       float *const *g_w_ih, float *const *g_w_hh, float *g_fc_w, float *g_fc_b, float *g_x,
                       void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * Command-driven free run of the LSTM surrogate (the results_LSTM track of NeuralNetwork.loop, Functions.py:
+ * 1196-1231): T steps on its own predictions and an externally given command sequence, one launch. `dims` as for
+ * fcr_lstm_forward with N = T (>= 1); H <= 52 and precision = FCR_PRECISION_FP32 only (FCR_EUNSUPPORTED otherwise).
+ *   window0 (B,10,5) scaled window [y_dot,p1,p2,z,u];  cmd (B,T) scaled commands;
+ *   gain    HOST float[4] or NULL (= 1): what the harness's scalers['output'].inverse_transform followed by
+ *           scalers['input'].transform amount to between steps (:1009, :1198), out_scale / in_scale per column;
+ *   noise   (B,T,4) additive output noise, or NULL;   xhat (B,T,4) the predictions.
+ * Step 0 runs window0 with the command column of its last row replaced by cmd[:,0] (as fcr_forward does with u0);
+ * step t >= 1 drops the oldest row and appends [gain * xhat_{t-1}, cmd[:,t]]; xhat_t = LSTM(window_t) + noise[:,t]
+ * (the fed-back value includes the noise, simulator_make_step :1004). The workspace does not grow with T. B = 0 is a
+ * no-op.
+ */
+int fcr_lstm_rollout_workspace_size(const fcr_dims *dims, size_t *bytes);
+int fcr_lstm_rollout(const fcr_dims *dims, const fcr_weights *w, const float *window0, const float *cmd,
+                     const float *gain, const float *noise, float *xhat, void *ws, size_t ws_bytes, void *stream);
 
 /*
  * Process-wide DEFAULTS of the per-call options (a field set to FCR_OPT_INHERIT takes them).
