@@ -19,8 +19,8 @@ _IN_TREE = os.path.join(_HERE, "lib", _LIB_NAME)
 LIB_PATH = os.environ.get("FCR_LIB") or _IN_TREE
 
 FCR_OK = 0
-# 7: fcr_closed_loop gains process_noise / meas_noise (NULL = none), fcr_lstm_rollout[_workspace_size] exported
-ABI_VERSION = 7
+# 8: fcr_feasibility + fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag (NULL = off)
+ABI_VERSION = 8
 PRECISION_FP32, PRECISION_F16 = 0, 1
 ERRORS = {-1: "FCR_EINVAL", -2: "FCR_EWORKSPACE", -3: "FCR_EHIP", -4: "FCR_EUNSUPPORTED"}
 
@@ -31,7 +31,7 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_get_small_batch_limit", "fcr_set_small_pipe_limit", "fcr_get_small_pipe_limit", "fcr_set_small_pipe_sets",
            "fcr_get_small_pipe_sets", "fcr_set_wide_keep_budget", "fcr_get_wide_keep_budget", "fcr_last_error",
            "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
-           "fcr_lstm_rollout")
+           "fcr_lstm_rollout", "fcr_feasibility_project")
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
 
@@ -78,6 +78,15 @@ class FcrWindows(ctypes.Structure):
     ]
 
 
+class FcrFeasibility(ctypes.Structure):
+    """fcr_feasibility (include/fcr.h): the parameters of the feasibility projection."""
+    _fields_ = [
+        ("p1_lo", ctypes.c_double), ("p1_hi", ctypes.c_double), ("p2_lo", ctypes.c_double), ("p2_hi", ctypes.c_double),
+        ("u_lo", ctypes.c_double), ("u_hi", ctypes.c_double), ("ts", ctypes.c_double),
+        ("substeps", ctypes.c_int32), ("expand", ctypes.c_int32), ("bisect", ctypes.c_int32),
+    ]
+
+
 class FcrClosedLoop(ctypes.Structure):
     _fields_ = [
         ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("ts", ctypes.c_double),
@@ -88,6 +97,8 @@ class FcrClosedLoop(ctypes.Structure):
         ("ref_scale", ctypes.c_double), ("out_scale", ctypes.c_double),
         ("x", ctypes.c_void_p), ("u", ctypes.c_void_p),
         ("process_noise", ctypes.c_void_p), ("meas_noise", ctypes.c_void_p),   # (B,T,5) fp64 each, or NULL
+        ("feasibility", ctypes.POINTER(FcrFeasibility)),                       # NULL = no recovery
+        ("u_nn", ctypes.c_void_p), ("feas_flag", ctypes.c_void_p),             # (B,T) fp64 / int32, with feasibility
     ]
 
 
@@ -142,6 +153,8 @@ def load() -> ctypes.CDLL:
         lib.fcr_lstm_rollout.restype = i32
         lib.fcr_closed_loop_run.argtypes = [ctypes.POINTER(FcrClosedLoop), vp]
         lib.fcr_closed_loop_run.restype = i32
+        lib.fcr_feasibility_project.argtypes = [ctypes.POINTER(FcrFeasibility), i32, vp, vp, vp, vp, vp, vp]
+        lib.fcr_feasibility_project.restype = i32
         lib.fcr_window_gather.argtypes = [ctypes.POINTER(FcrWindows), i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_window_gather.restype = i32
         lib.fcr_fnn_workspace_size.argtypes = [i32, i32, ctypes.POINTER(sz)]

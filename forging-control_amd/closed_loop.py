@@ -11,8 +11,11 @@ forging-control_amd/csrc/fcr_closed_loop.h). do-mpc's process and measurement no
 Functions.py:1175-1183) are optional pre-drawn inputs of that launch: :func:`harness_noise` draws them in the
 reference's order. :meth:`ClosedLoop.loop` adds the harness's second track, the LSTM surrogate stepped beside
 the press on its own predictions and the controller's command (``results_LSTM``, Functions.py:1196-1231), as
-one more launch (``fcr_lstm_rollout``, csrc/fcr_lstm_rollout.h). Feasibility recovery (CasADi/IPOPT) is not
-part of it.
+one more launch (``fcr_lstm_rollout``, csrc/fcr_lstm_rollout.h). The reference's feasibility recovery
+(``FeasibilityRecovery.feasibility_recover``, a CasADi/IPOPT solve per step) is :class:`FeasibilityRecovery`: its
+NLP is the projection of one command onto the set that keeps both pressures inside their bounds over the next two
+steps, which ``csrc/fcr_feasibility.h`` searches on the GPU, alone (``project``) or inside the loop's launch
+(``feasibility=``).
 """
 from __future__ import annotations
 
@@ -68,6 +71,48 @@ def _scale(s):
     return np.atleast_1d(np.asarray(getattr(s, "scale_", s), dtype=np.float64))
 
 
+class FeasibilityRecovery:
+    """The reference's feasibility recovery (UL/Main.py:584-657) as a projection on the GPU.
+
+    The NLP has one scalar ``u``; its slacks are in the cost only, so it is ``min (u_nn - u)^2`` subject to
+    ``p1`` and ``p2`` staying inside their bounds after one and two RK4 steps of the non-smooth ``forging_model``
+    with ``u`` held. ``project(x (B,5), u_nn (B)) -> (u (B), flag (B) int32)``: flag 0 = ``u_nn`` is feasible and is
+    returned bit for bit (also outside ``u_bounds``: the NLP does not bound ``u``); 1 = corrected to the nearest
+    feasible command found by probing ``u_nn -/+ (u_hi - u_lo)/2^expand * 2^k`` (clipped to ``u_bounds``) for
+    k = 0..expand and bisecting ``bisect`` times towards ``u_nn``; 2 = no probe is feasible and ``u`` is
+    ``clip(u_nn, *u_bounds)``, the reference's ``except`` branch. The search returns the nearest feasible command
+    wherever the feasible set is an interval on the probed side."""
+
+    def __init__(self, p1=(0.0, 32e6), p2=(0.0, 32e6), u_bounds=(-0.2, 0.2), ts: float = TS_REFERENCE,
+                 substeps: int = SUBSTEPS_REFERENCE, expand: int = 10, bisect: int = 30):
+        self.p1, self.p2 = (float(p1[0]), float(p1[1])), (float(p2[0]), float(p2[1]))
+        self.u_bounds = (float(u_bounds[0]), float(u_bounds[1]))
+        self.ts, self.substeps, self.expand, self.bisect = float(ts), int(substeps), int(expand), int(bisect)
+
+    def struct(self) -> _native.FcrFeasibility:
+        return _native.FcrFeasibility(*self.p1, *self.p2, *self.u_bounds, self.ts, self.substeps, self.expand,
+                                      self.bisect)
+
+    def project(self, x: torch.Tensor, u_nn: torch.Tensor, return_violation: bool = False):
+        """``return_violation``: also return ``v (B)``, the violation at the returned ``u`` (feasible iff <= 0)."""
+        dev = x.device
+        if dev.type != "cuda" or u_nn.device != dev:
+            raise RuntimeError(f"FeasibilityRecovery runs on a ROCm device only (x on {x.device}, u_nn on {u_nn.device})")
+        if x.dim() != 2 or x.shape[1] != 5 or u_nn.dim() != 1 or u_nn.shape[0] != x.shape[0]:
+            raise ValueError(f"x must be (B,5) and u_nn (B,); got {tuple(x.shape)}, {tuple(u_nn.shape)}")
+        B = x.shape[0]
+        xc, uc = x.to(torch.float64).contiguous(), u_nn.to(torch.float64).contiguous()
+        u = torch.empty(B, dtype=torch.float64, device=dev)
+        flag = torch.empty(B, dtype=torch.int32, device=dev)
+        v = torch.empty(B, dtype=torch.float64, device=dev) if return_violation else None
+        f = self.struct()
+        _native.check(_native.load().fcr_feasibility_project(
+            ctypes.byref(f), B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
+            None if v is None else v.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+            "fcr_feasibility_project")
+        return (u, flag, v) if return_violation else (u, flag)
+
+
 class ClosedLoop:
     """Controller + press for B trajectories over T steps: ``run(x0 (B,5), ref (B,T))`` ->
     ``(x (B,T+1,5), u (B,T))`` as fp64 device tensors.
@@ -85,12 +130,18 @@ class ClosedLoop:
         self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
-            meas_noise: torch.Tensor | None = None):
+            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None):
         """``process_noise`` / ``meas_noise``: (B,T,5) pre-drawn ``w0`` / ``v0`` (:func:`harness_noise`), or None.
         ``w`` is in the units of x_dot and is held over the step: every RK4 stage evaluates f(x,u) + w[b,t].
         ``x[:,t+1]`` records x_{t+1} + v[b,t]; the controller reads that record, the press integrates on from the
         unperturbed state. (The smooth model measures p_eff, template_model.py:154-155; the record here is p + v.)
-        Without noise the call returns exactly what it always did."""
+        Without noise the call returns exactly what it always did.
+
+        ``feasibility``: a :class:`FeasibilityRecovery`; every step then projects the controller's command from the
+        state the controller reads (under ``meas_noise`` the noisy record) and steps the press with the projected
+        command. The call then returns ``(x, u, info)``: ``u`` the projected commands, ``info = {"u_nn": (B,T) the
+        controller's raw commands, "flag": (B,T) int32 the projection's flags}``. With ``None`` it returns ``(x, u)``
+        as it always did."""
         dev = x0.device
         if dev.type != "cuda" or ref.device != dev:
             raise RuntimeError(f"ClosedLoop runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
@@ -114,18 +165,24 @@ class ClosedLoop:
         x = torch.empty(B, T + 1, 5, dtype=torch.float64, device=dev)
         u = torch.empty(B, T, dtype=torch.float64, device=dev)
         p = lambda t: t.data_ptr()
+        feas, info = (), None
+        if feasibility is not None:
+            info = {"u_nn": torch.empty(B, T, dtype=torch.float64, device=dev),
+                    "flag": torch.empty(B, T, dtype=torch.int32, device=dev)}
+            f_struct = feasibility.struct()                  # stays alive over the call below
+            feas = (ctypes.pointer(f_struct), p(info["u_nn"]), p(info["flag"]))
         args = _native.FcrClosedLoop(B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp),
                                      p(b_inp), p(W_out), W_inp.shape[0], (ctypes.c_double * 2)(*self.in_scale),
                                      self.ref_scale, self.out_scale, p(x), p(u),
-                                     *(None if n is None else p(n) for n in noise))
+                                     *(None if n is None else p(n) for n in noise), *feas)
         _native.check(_native.load().fcr_closed_loop_run(ctypes.byref(args),
                                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                       "fcr_closed_loop_run")
-        return x, u
+        return (x, u) if info is None else (x, u, info)
 
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
              process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
-             lstm_noise: torch.Tensor | None = None):
+             lstm_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None):
         """``NeuralNetwork.loop``'s two tracks for B trajectories (Functions.py:1116-1273) in two launches: the press
         under the controller (:meth:`run`) and the LSTM surrogate free-running beside it on its own predictions and
         the press's commands (``inference.simulate_rollout`` on that run's ``u``).
@@ -134,8 +191,10 @@ class ClosedLoop:
         ``'output'`` (scale_ of [y_dot, p1, p2, z]). ``lstm_noise`` (B,T,4): the scaled ``w0_NN`` (the reference
         draws it with zero std). Returns ``(results, results_LSTM)``, dicts of fp64 device tensors keyed as the
         reference's (:1266-1273): ``results`` y, y_dot, p1, p2, z (B,T+1) and ref, u (B,T); ``results_LSTM`` y_dot,
-        p1, p2, z (B,T+1), row 0 = x0[:,1:5]."""
-        x, u = self.run(x0, ref, process_noise, meas_noise)
+        p1, p2, z (B,T+1), row 0 = x0[:,1:5]. With ``feasibility`` (:meth:`run`) ``results['u']`` holds the projected
+        commands, which also drive the surrogate's track (Functions.py:1196), and ``results`` gains ``u_nn`` and
+        ``feas_flag`` (B,T)."""
+        x, u, *info = self.run(x0, ref, process_noise, meas_noise, feasibility)
         dev = x.device
         s_in, s_out = _scale(model_scalers["input"]), _scale(model_scalers["output"])
         if s_in.shape != (5,) or s_out.shape != (4,):
@@ -144,6 +203,8 @@ class ClosedLoop:
         B, T = u.shape
         results = {"y": x[:, :, 0], "y_dot": x[:, :, 1], "p1": x[:, :, 2], "p2": x[:, :, 3], "z": x[:, :, 4],
                    "ref": ref.to(torch.float64), "u": u}
+        if info:
+            results["u_nn"], results["feas_flag"] = info[0]["u_nn"], info[0]["flag"]
         first = x[:, 0, 1:5]
         track = torch.empty(B, T + 1, 4, dtype=torch.float64, device=dev)
         track[:, 0] = first

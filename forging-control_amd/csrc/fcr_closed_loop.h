@@ -1,7 +1,7 @@
 // fcr_closed_loop.h — the NN controller driving the press, all T steps of B trajectories in one launch
 // (SURVEY.md §8(f) ranks 1 + 2 together: the closed-loop evaluation the plant row exists for).
 //
-// Reference: NeuralNetwork.loop (Functions.py:1075-1240) without feasibility recovery, per step t:
+// Reference: NeuralNetwork.loop (Functions.py:1075-1240; with its feasibility recovery: fcr_feasibility.h), per step t:
 //   X = [y_dot, z, ref_t]; X_new = scalers['input'].transform(X) with the last column replaced by
 //   scalers['y_dot'].transform(ref_t) (NN_make_step, Functions.py:1594-1598); u = scalers['output']
 //   .inverse_transform(FNN(float32(X_new))) (:1601-1604); x_{t+1} = plant(x_t, u) (:1178-1179; here the

@@ -1,16 +1,36 @@
 // fcr_rows.hip — C ABI of the SURVEY.md §8(f) rows that need no rollout state: the batched press plant
-// (fcr_plant.h), the controller + press closed loop (fcr_closed_loop.h) and the training-window gather
-// (fcr_window.h). Validation before any device call; stream-ordered launches; no allocation.
+// (fcr_plant.h), the controller + press closed loop (fcr_closed_loop.h), its feasibility recovery
+// (fcr_feasibility.h) and the training-window gather (fcr_window.h). Validation before any device call; stream-ordered launches; no allocation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fcr.h"
 #include "fcr_closed_loop.h"
+#include "fcr_feasibility.h"
 #include "fcr_host.h"
 #include "fcr_plant.h"
 #include "fcr_window.h"
 
 using namespace fcr;
+
+namespace {
+
+// fcr_feasibility -> the kernels' arguments (bounds scaled as the reference's NLP scales them), or a message
+int feasibility_args(const char *who, const fcr_feasibility *f, feasibility::FeasArgs *out) {
+    if (!(f->p1_lo < f->p1_hi)) return fail(FCR_EINVAL, "%s: p1 bounds lo=%g must be < hi=%g", who, f->p1_lo, f->p1_hi);
+    if (!(f->p2_lo < f->p2_hi)) return fail(FCR_EINVAL, "%s: p2 bounds lo=%g must be < hi=%g", who, f->p2_lo, f->p2_hi);
+    if (!(f->u_lo < f->u_hi)) return fail(FCR_EINVAL, "%s: u_lo=%g must be < u_hi=%g", who, f->u_lo, f->u_hi);
+    if (f->substeps < 1 || f->substeps > 4096) return fail(FCR_EINVAL, "%s: feasibility substeps=%d must be 1..4096", who, f->substeps);
+    if (!(f->ts > 0.0) || f->ts > 1e6) return fail(FCR_EINVAL, "%s: feasibility ts=%g must be a positive time step", who, f->ts);
+    if (f->expand < 1 || f->expand > 20) return fail(FCR_EINVAL, "%s: expand=%d must be 1..20", who, f->expand);
+    if (f->bisect < 1 || f->bisect > 60) return fail(FCR_EINVAL, "%s: bisect=%d must be 1..60", who, f->bisect);
+    *out = feasibility::FeasArgs{f->p1_lo * feasibility::kPScale, f->p1_hi * feasibility::kPScale,
+                                 f->p2_lo * feasibility::kPScale, f->p2_hi * feasibility::kPScale,
+                                 f->u_lo, f->u_hi, f->ts / f->substeps, f->substeps, f->expand, f->bisect};
+    return FCR_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -78,11 +98,37 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
     if ((((uintptr_t)c->x0) | ((uintptr_t)c->ref) | ((uintptr_t)c->x) | ((uintptr_t)c->u)) & 7)
         return fail(FCR_EINVAL, "fcr_closed_loop_run: fp64 buffers must be 8-byte aligned");
     if ((((uintptr_t)c->process_noise) | ((uintptr_t)c->meas_noise)) & 7)
-        return fail(FCR_EINVAL, "fcr_closed_loop_run: noise buffers must be 8-byte aligned (fp64)");    closed_loop::ClArgs a{c->B, c->T, c->substeps, c->ctrl_hidden, c->ts / c->substeps, c->x0, c->ref,
+        return fail(FCR_EINVAL, "fcr_closed_loop_run: noise buffers must be 8-byte aligned (fp64)");
+    feasibility::FeasArgs fa{};
+    if (c->feasibility) {
+        if (const int rc = feasibility_args("fcr_closed_loop_run", c->feasibility, &fa)) return rc;
+        if (c->T > 0 && (!c->u_nn || !c->feas_flag))
+            return fail(FCR_EINVAL, "fcr_closed_loop_run: u_nn or feas_flag is NULL with feasibility set");
+        if ((((uintptr_t)c->u_nn) & 7) || (((uintptr_t)c->feas_flag) & 3))
+            return fail(FCR_EINVAL, "fcr_closed_loop_run: u_nn must be 8-byte and feas_flag 4-byte aligned");
+    }
+    closed_loop::ClArgs a{c->B, c->T, c->substeps, c->ctrl_hidden, c->ts / c->substeps, c->x0, c->ref,
                           c->ctrl_w_inp, c->ctrl_b_inp, c->ctrl_w_out, c->in_scale[0], c->in_scale[1],
                           c->ref_scale, c->out_scale, c->x, c->u};
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((c->B + closed_loop::kClBlock - 1) / closed_loop::kClBlock);
+    if (c->T > 0 && c->feasibility) {                        // recovery between controller and press: kernels of their own
+        const dim3 block(closed_loop::kClBlock);
+        const bool noise = c->process_noise || c->meas_noise;
+        if (c->smooth && noise)
+            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<true, true>), grid, block, 0, s, a, fa,
+                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
+        else if (c->smooth)
+            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<true, false>), grid, block, 0, s, a, fa,
+                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
+        else if (noise)
+            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<false, true>), grid, block, 0, s, a, fa,
+                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
+        else
+            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<false, false>), grid, block, 0, s, a, fa,
+                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
+        return launch_check("closed_loop_recover_kernel");
+    }
     if (c->T > 0 && (c->process_noise || c->meas_noise)) {   // the harness's noise: a kernel of its own
         if (c->smooth)
             hipLaunchKernelGGL(closed_loop::closed_loop_noise_kernel<true>, grid, dim3(closed_loop::kClBlock), 0, s, a,
@@ -97,6 +143,21 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
     else
         hipLaunchKernelGGL(closed_loop::closed_loop_kernel<false>, grid, dim3(closed_loop::kClBlock), 0, s, a);
     return launch_check("closed_loop_kernel");
+}
+
+int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,
+                            int32_t *flag, double *v, void *stream) {
+    if (!f) return fail(FCR_EINVAL, "fcr_feasibility_project: parameters is NULL");
+    if (B < 0) return fail(FCR_EINVAL, "fcr_feasibility_project: B=%d must be >= 0", B);
+    feasibility::FeasArgs fa{};
+    if (const int rc = feasibility_args("fcr_feasibility_project", f, &fa)) return rc;
+    if (B == 0) return FCR_OK;
+    if (!x || !u_nn || !u || !flag) return fail(FCR_EINVAL, "fcr_feasibility_project: a required pointer is NULL");
+    if (((((uintptr_t)x) | ((uintptr_t)u_nn) | ((uintptr_t)u) | ((uintptr_t)v)) & 7) || (((uintptr_t)flag) & 3))
+        return fail(FCR_EINVAL, "fcr_feasibility_project: fp64 buffers must be 8-byte and flag 4-byte aligned");
+    hipLaunchKernelGGL(feasibility::feasibility_project_kernel, dim3((B + feasibility::kFeasBlock - 1) / feasibility::kFeasBlock),
+                       dim3(feasibility::kFeasBlock), 0, (hipStream_t)stream, fa, B, x, u_nn, u, flag, v);
+    return launch_check("feasibility_project_kernel");
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FCR_ABI_VERSION 7   /* 7: fcr_closed_loop gains process_noise / meas_noise; fcr_lstm_rollout */
+#define FCR_ABI_VERSION 8   /* 8: fcr_feasibility, fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag */
 
 enum {
     FCR_OK = 0,
@@ -178,9 +178,10 @@ int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smo
 
 /*
  * Batched closed-loop evaluation (SURVEY.md §8(f) ranks 1 + 2): NeuralNetwork.loop (Functions.py:
- * 1075-1240) without feasibility recovery — per step the FNN controller on the MaxAbs-scaled
- * [y_dot, z, ref] (NN_make_step, :1560-1613; fp32 like torch) and the press advanced by the RK4
- * integrator of fcr_plant_rk4 (in place of do-mpc's CVODES) — for B trajectories × T steps, one launch.
+ * 1075-1240) — per step the FNN controller on the MaxAbs-scaled [y_dot, z, ref] (NN_make_step, :1560-1613;
+ * fp32 like torch), optionally the feasibility recovery of its command (fcr_feasibility, below), and the
+ * press advanced by the RK4 integrator of fcr_plant_rk4 (in place of do-mpc's CVODES) — for B trajectories
+ * × T steps, one launch.
  *   x0 (B,5), ref (B,T) unscaled speed references (NeuralNetwork.tvp_fun, :926-966, computed by the
  *   caller); controller weights as fcr_weights; in_scale = scalers['input'].scale_[0:2] (y_dot, z),
  *   ref_scale = scalers['y_dot'].scale_, out_scale = scalers['output'].scale_ (UL/Main.py:237-256);
@@ -193,7 +194,14 @@ int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smo
  *   meas_noise (B,T,5) fp64: x[:,t+1] records x_{t+1} + meas_noise[b,t], the controller reads that record at
  *     step t+1, and the integration continues from the unperturbed state. (The smooth model measures p_eff, not p,
  *     template_model.py:154-155; here the record is p + v.)
+ * Optional feasibility recovery (ABI v8; NULL = off, so a zero-initialised struct runs the loop as before):
+ *   feasibility  the projection's parameters; when set, every step projects the controller's command from the
+ *     state the controller reads (under meas_noise the noisy record, all five components: Functions.py:1170) and
+ *     the press is stepped with the projected command; u (B,T) then holds the projected commands;
+ *   u_nn (B,T) fp64 the controller's raw commands, feas_flag (B,T) int32 the projection's flags; both are
+ *     required when feasibility is set and ignored otherwise.
  */
+typedef struct fcr_feasibility fcr_feasibility;
 typedef struct fcr_closed_loop {
     int32_t B, T;
     double ts;
@@ -205,9 +213,41 @@ typedef struct fcr_closed_loop {
     double ref_scale, out_scale;
     double *x, *u;
     const double *process_noise, *meas_noise; /* (B,T,5) each, or NULL (ABI v7) */
+    const fcr_feasibility *feasibility;       /* NULL = no recovery (ABI v8) */
+    double *u_nn;                             /* (B,T), with feasibility */
+    int32_t *feas_flag;                       /* (B,T), with feasibility */
 } fcr_closed_loop;
 
 int fcr_closed_loop_run(const fcr_closed_loop *args, void *stream);
+
+/*
+ * Feasibility recovery (FeasibilityRecovery.feasibility_recover; the NLP of UL/Main.py:584-657) as a projection.
+ * The NLP's slacks are in its cost only, so it is min (u_nn - u)^2 over one scalar u under
+ *   p1_lo <= p1(X1), p1(X2) <= p1_hi,  p2_lo <= p2(X1), p2(X2) <= p2_hi,  X1 = F(x,u), X2 = F(X1,u),
+ * F = `substeps` RK4 stages over `ts` of the NON-smooth forging_model with u held (Ruge_Kuta, Functions.py:1743-1781).
+ * With pressures scaled by 1/32e6, v(x,u) = the largest of max(lo - p, p - hi) over the four pressures; u is feasible
+ * iff v <= 0 (NaN: infeasible). Per state, in fp64:
+ *   flag 0  v(x, u_nn) <= 0: u = u_nn bit for bit, also outside [u_lo, u_hi] (the NLP does not bound u);
+ *   flag 1  for k = 0..expand probe clip(u_nn -/+ d·2^k), d = (u_hi - u_lo)/2^expand, clipped to [u_lo, u_hi]; at the
+ *           first k with a feasible probe (both: the nearer, ties to the lower) bisect `bisect` times between it and
+ *           the previous probe on its side (u_nn at k = 0); u = the feasible end of the bracket;
+ *   flag 2  no probe feasible: u = clip(u_nn, u_lo, u_hi) (the reference's `except` branch).
+ * The result is the nearest feasible command wherever the feasible set is an interval on the probed side.
+ * Reference values: bounds 0 / 32e6 (UL/Main.py:118-119), u_lo/u_hi = -/+0.2 (Functions.py:1533), ts = 1e-3,
+ * substeps = 4; expand = 10, bisect = 30 (a final bracket of 0.4/2^10/2^30).
+ */
+struct fcr_feasibility {
+    double p1_lo, p1_hi, p2_lo, p2_hi; /* Pa; lo < hi                        */
+    double u_lo, u_hi;                 /* u_lo < u_hi                        */
+    double ts;                         /* the projection's own step          */
+    int32_t substeps;                  /* 1..4096                            */
+    int32_t expand;                    /* 1..20                              */
+    int32_t bisect;                    /* 1..60                              */
+};
+
+/* x (B,5), u_nn (B) -> u (B), flag (B) int32 and, unless NULL, v (B) = v(x, u) at the returned u. B = 0 is a no-op. */
+int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,
+                            int32_t *flag, double *v, void *stream);
 
 /*
  * Training-sample windows: the tables of the concatenated per-trajectory

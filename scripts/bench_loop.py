@@ -8,6 +8,7 @@
   torch between them (``inference._rollout_by_steps``); the two results are compared as well.
 
 Each figure is the median of ``--repeats`` timed calls after one warm-up call; the single timings are kept beside it.
+``--recovery`` times the loop with feasibility recovery instead (:func:`recovery`), one JSON line as well.
 """
 import argparse
 import json
@@ -41,13 +42,75 @@ def timed(fn, repeats):
     return {"ms": float(np.median(out)), "each_ms": [round(v, 4) for v in out]}
 
 
+def recovery(a):
+    """--recovery: ``ClosedLoop.run`` with and without ``feasibility=FeasibilityRecovery()`` and ``project`` alone.
+
+    * ``feasible``: B x T with every trajectory's working-stroke reference held (no step is flagged; the line reports
+      the count): the price of the 32-right-hand-side check beside the plant step's 16.
+    * ``corrections``: the inputs of tests/test_closed_loop.py::test_gpu_closed_loop_matches_oracle (300 trajectories,
+      120 steps, smooth=False) tiled to B: waves with an infeasible lane run the search.
+    * ``clean`` / ``w_v``: the same B x T without recovery, as the default mode times them.
+    * ``project``: the fixture tests/golden/feasibility_cases.npz tiled to B."""
+    B, T = a.batch, a.steps
+    w = np.load(os.path.join(ROOT, "tests", "golden", "weights_ref.npz"))
+    ctrl = fca.FNNModel(3, 50, 1, 1).to(DEV)
+    with torch.no_grad():
+        ctrl.fc_inp.weight.copy_(torch.tensor(w["W_inp"]))
+        ctrl.fc_inp.bias.copy_(torch.tensor(w["b_inp"]))
+        ctrl.fc_out.weight.copy_(torch.tensor(w["W_out"]))
+    fr = fca.FeasibilityRecovery()
+    dev = lambda v: torch.tensor(v, device=DEV)
+    rng = np.random.default_rng(0)
+    x0 = np.zeros((B, 5))
+    x0[:, 2:4] = rng.uniform(1e6, 4e6, (B, 2))
+    ref = fca.closed_loop.reference_speeds(64, T, 1e-3, 1, 100)[rng.integers(0, 64, B)]
+    cl = fca.ClosedLoop(ctrl, SCALERS)
+    x0_d, ref_d, held_d = dev(x0), dev(ref), dev(np.repeat(ref[:, :1], T, axis=1))
+    g = torch.Generator(device=DEV).manual_seed(0)
+    draw = lambda std: torch.randn(B, T, 5, dtype=torch.float64, device=DEV, generator=g) * torch.tensor(std, device=DEV)
+    wn, vn = draw(PROCESS_STD), draw(MEAS_STD)
+    out = {"B": B, "T": T, "clean": timed(lambda: cl.run(x0_d, ref_d), a.repeats),
+           "w_v": timed(lambda: cl.run(x0_d, ref_d, process_noise=wn, meas_noise=vn), a.repeats)}
+    del wn, vn
+    out["feasible_clean"] = timed(lambda: cl.run(x0_d, held_d), a.repeats)
+    out["feasible"] = timed(lambda: cl.run(x0_d, held_d, feasibility=fr), a.repeats)
+    flag = cl.run(x0_d, held_d, feasibility=fr)[2]["flag"]
+    out["feasible"]["flagged_steps"] = int((flag != 0).sum())
+    out["feasible"]["over_clean"] = out["feasible"]["ms"] / out["feasible_clean"]["ms"]
+    del flag
+
+    r4 = np.random.default_rng(4)                      # test_gpu_closed_loop_matches_oracle's inputs
+    xs = np.zeros((300, 5))
+    xs[:, 2] = r4.uniform(1e6, 4e6, 300)
+    xs[:, 3] = r4.uniform(1e6, 4e6, 300)
+    tile = np.arange(B) % 300
+    xc_d, rc_d = dev(xs[tile]), dev(fca.closed_loop.reference_speeds(300, 120, 1e-3, 1, 100)[tile])
+    cn = fca.ClosedLoop(ctrl, SCALERS, smooth=False)
+    cor = {"B": B, "T": 120, "plain": timed(lambda: cn.run(xc_d, rc_d), a.repeats),
+           "recovery": timed(lambda: cn.run(xc_d, rc_d, feasibility=fr), a.repeats)}
+    flag = cn.run(xc_d, rc_d, feasibility=fr)[2]["flag"]
+    cor["flagged_steps"] = [int((flag == k).sum()) for k in (1, 2)]
+    cor["over_plain"] = cor["recovery"]["ms"] / cor["plain"]["ms"]
+    out["corrections"] = cor
+
+    c = np.load(os.path.join(ROOT, "tests", "golden", "feasibility_cases.npz"))
+    tile = np.arange(B) % c["x"].shape[0]
+    xp_d, up_d = dev(c["x"][tile]), dev(c["u_nn"][tile])
+    out["project"] = {"B": B, "flags_0_1_2": [int((c["flag"][tile] == k).sum()) for k in range(3)],
+                      **timed(lambda: fr.project(xp_d, up_d), a.repeats)}
+    print(json.dumps({"metric": "harness loop, feasibility recovery", "device": torch.cuda.get_device_name(0), **out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--rollout-batch", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--recovery", action="store_true", help="time the loop with feasibility recovery instead")
     a = ap.parse_args()
+    if a.recovery:
+        return recovery(a)
     B, T = a.batch, a.steps
     w = np.load(os.path.join(ROOT, "tests", "golden", "weights_ref.npz"))
     ctrl = fca.FNNModel(3, 50, 1, 1).to(DEV)

@@ -1,0 +1,184 @@
+"""GPU: the feasibility projection (csrc/fcr_feasibility.h) alone and inside the closed loop, against the NumPy
+restatement (tests/feasibility_np.py on oracle/plant_np.py) and its fixture (tests/golden/feasibility_cases.npz)."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import forging_control_amd as fca
+from conftest import GOLDEN
+from feasibility_np import closed_loop_recover, violation
+from test_closed_loop import SCALERS, ctrl_weights
+from test_gpu_loop import MEAS_STD, PROCESS_STD, gpu_controller, load_weights, lstm_model
+from test_harness import OUT_MAXABS
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+U_LO, U_HI = -0.2, 0.2
+P_HI = 32e6
+V_SLACK = 1e-9            # kernel against NumPy plant at the boundary: the tolerance tests/test_plant.py gives the fp64 plant
+t = lambda a: torch.tensor(a, device=DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def cases():
+    return dict(np.load(os.path.join(GOLDEN, "feasibility_cases.npz")))
+
+
+def oracle(x0, ref, smooth, w=None, v=None):
+    return closed_loop_recover(x0, ref, *ctrl_weights(), SCALERS["input"][:2], SCALERS["y_dot"], SCALERS["output"],
+                               smooth=smooth, process_noise=w, meas_noise=v)
+
+
+def loop_errors(x, u, xr, ur):
+    scale = np.abs(xr).reshape(-1, 5).max(0)
+    return (np.abs(x - xr).reshape(-1, 5) / scale).max(0), np.abs(u - ur).max() / np.abs(ur).max()
+
+
+@functools.lru_cache(maxsize=None)
+def press_case():
+    """The inputs of test_closed_loop.py::test_gpu_closed_loop_matches_oracle."""
+    B, T = 300, 120
+    rng = np.random.default_rng(4)
+    x0 = np.zeros((B, 5))
+    x0[:, 2] = rng.uniform(1e6, 4e6, B)
+    x0[:, 3] = rng.uniform(1e6, 4e6, B)
+    return x0, fca.closed_loop.reference_speeds(B, T, 1e-3, 1, 100)
+
+
+def infeasible_starts(B, T):
+    """Fixture states the loop met with an infeasible command, each under the (held) reference it was met under:
+    recovery acts from step 0."""
+    c = cases()
+    idx = np.flatnonzero(c["flag"][:int(c["n_loop"])] == 1)[:B]
+    assert idx.size == B
+    return c["x"][idx], np.repeat(c["ref_loop"][idx][:, None], T, axis=1)
+
+
+def test_projection_matches_the_fixture():
+    c = cases()
+    x, u_nn, ur, fr = c["x"], c["u_nn"], c["u"], c["flag"]
+    u, flag, v = fca.FeasibilityRecovery().project(t(x), t(u_nn), return_violation=True)
+    assert flag.dtype == torch.int32 and u.dtype == torch.float64 and u.shape == flag.shape == v.shape == (x.shape[0],)
+    u2, flag2 = fca.FeasibilityRecovery().project(t(x), t(u_nn))           # v is optional
+    assert torch.equal(u2, u) and torch.equal(flag2, flag)
+    u, flag, v = u.cpu().numpy(), flag.cpu().numpy(), v.cpu().numpy()
+    assert np.array_equal(flag, fr), np.flatnonzero(flag != fr)
+    f0, f1, f2 = fr == 0, fr == 1, fr == 2
+    assert np.array_equal(u[f0], u_nn[f0])                                  # bit for bit, also outside u_bounds
+    assert np.array_equal(u[f2], np.clip(u_nn[f2], U_LO, U_HI))
+    d1 = np.abs(u[f1] - ur[f1]).max()
+    vu = violation(x, u)
+    v_off = violation(x[f1], u[f1] + np.sign(u_nn[f1] - u[f1]) * 1e-9)
+    print(f"flag 1: max |u - u_ref| {d1:.3g}; v(u) max {vu[f1].max():.3g}; v(u + 1e-9 towards u_nn) min {v_off.min():.3g}; "
+          f"max |v_kernel - v_numpy| {np.abs(v - vu).max():.3g}")
+    assert d1 <= 4e-10                                                       # two final brackets of 0.2 / 2^30
+    assert np.all(vu[f1] <= V_SLACK) and np.all(v_off > -V_SLACK)            # feasible, and nearest to 1e-9
+    assert np.all(vu[f0] <= 0) and np.all(vu[f2] > 0)
+    assert np.abs(v - vu).max() <= V_SLACK
+
+
+def test_projection_honours_its_parameters():
+    """Other bounds, command range and search depths than the defaults, against the restatement."""
+    from feasibility_np import project
+    c = cases()
+    x, u_nn = c["x"][::3], c["u_nn"][::3]
+    kw = dict(p1=(1e6, 30e6), p2=(0.5e6, 31e6), u_bounds=(-0.1, 0.15), ts=1e-3, substeps=2, expand=6, bisect=20)
+    ur, fr, _ = project(x, u_nn, **kw)
+    vr = violation(x, u_nn, kw["p1"], kw["p2"], kw["ts"], kw["substeps"])
+    sure = np.abs(vr) > V_SLACK
+    u, flag = fca.FeasibilityRecovery(**kw).project(t(x), t(u_nn))
+    u, flag = u.cpu().numpy(), flag.cpu().numpy()
+    assert len(set(fr)) == 3 and not np.array_equal(fr, c["flag"][::3])      # the parameters matter
+    assert np.array_equal(flag[sure], fr[sure])
+    ok = sure & (fr == 1)
+    assert np.abs(u[ok] - ur[ok]).max() <= 2 * 0.125 / 2 ** 20              # two final brackets
+    assert np.array_equal(u[sure & (fr != 1)], ur[sure & (fr != 1)])
+
+
+def test_closed_loop_with_recovery_matches_oracle():
+    x0, ref = press_case()
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS, smooth=False)
+    x, u, info = cl.run(t(x0), t(ref), feasibility=fca.FeasibilityRecovery())
+    xr, ur, unr, flr = oracle(x0, ref, False)
+    x, u, u_nn, flag = x.cpu().numpy(), u.cpu().numpy(), info["u_nn"].cpu().numpy(), info["flag"].cpu().numpy()
+    assert u_nn.shape == flag.shape == (300, 120) and flag.dtype == np.int32
+    assert np.array_equal(x[:, 0], x0)
+    err, uerr = loop_errors(x, u, xr, ur)
+    p = x[:, 1:, 2:4]
+    print(f"state err {err}, u err {uerr:.3g}; flagged {np.count_nonzero(flag)} (oracle {np.count_nonzero(flr)}), "
+          f"largest |du| {np.abs(u - u_nn).max():.3g}; p in [{p.min():.3g}, {p.max():.3g}]")
+    assert np.all(err < 1e-5), err
+    assert uerr <= 1e-5
+    assert np.abs(u_nn - unr).max() <= 1e-5 * np.abs(unr).max()
+    assert np.count_nonzero(flag == 1) >= 200 and not np.any(flag == 2)
+    assert np.array_equal(u[flag == 0], u_nn[flag == 0]) and np.all(u[flag == 1] != u_nn[flag == 1])
+    assert p.min() >= -V_SLACK * P_HI and p.max() <= P_HI + V_SLACK * P_HI  # constraint-safe from step 1 on
+    xp, _ = cl.run(t(x0), t(ref))
+    assert xp[:, :, 2].min().item() < -1e6                                   # the plain loop cavitates
+
+
+def test_noisy_smooth_loop_projects_from_the_noisy_record():
+    B, T = 70, 80
+    x0, ref = infeasible_starts(B, T)
+    w, v = fca.closed_loop.harness_noise(B, T, PROCESS_STD, MEAS_STD, np.random.RandomState(7))
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS, smooth=True)
+    x, u, info = cl.run(t(x0), t(ref), process_noise=t(w), meas_noise=t(v), feasibility=fca.FeasibilityRecovery())
+    xr, ur, unr, flr = oracle(x0, ref, True, w, v)
+    assert np.all(flr[:, 0] == 1) and np.isfinite(xr).all()                  # recovery acts from step 0
+    x, u, u_nn, flag = x.cpu().numpy(), u.cpu().numpy(), info["u_nn"].cpu().numpy(), info["flag"].cpu().numpy()
+    err, uerr = loop_errors(x, u, xr, ur)
+    # a loop whose projection reads only the noisy y_dot and z (what the controller needs) is told apart
+    _, uw, _, _ = closed_loop_recover(x0, ref, *ctrl_weights(), SCALERS["input"][:2], SCALERS["y_dot"],
+                                      SCALERS["output"], smooth=True, process_noise=w, meas_noise=v,
+                                      project_reads_record=False)
+    print(f"state err {err}, u err {uerr:.3g}; flagged {np.count_nonzero(flag)} (oracle {np.count_nonzero(flr)}); "
+          f"u moved by the three other measured components {np.abs(ur - uw).max():.3g}")
+    assert np.all(err < 1e-5), err
+    assert uerr <= 1e-5
+    assert np.array_equal(flag[:, 0], flr[:, 0])
+    assert np.abs(u_nn - unr).max() <= 1e-5 * np.abs(unr).max()
+    assert np.abs(ur - uw).max() > 1e-3 * np.abs(ur).max()
+
+
+def test_unflagged_run_is_the_plain_run():
+    x0, ref = press_case()
+    ref = ref[:, :20]
+    assert not oracle(x0, ref, True)[3].any()                                # nothing to recover, on the CPU
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS, smooth=True)
+    xp, up = cl.run(t(x0), t(ref))
+    x, u, info = cl.run(t(x0), t(ref), feasibility=fca.FeasibilityRecovery())
+    assert not info["flag"].any() and torch.equal(info["u_nn"], u)
+    assert torch.equal(u, up)                                                # bit for bit
+    scale = xp.abs().reshape(-1, 5).amax(0)
+    err = ((x - xp).abs().reshape(-1, 5) / scale).amax(0)
+    print(f"x against the plain run: bit-identical {torch.equal(x, xp)}, err {err.cpu().numpy()}")
+    assert torch.all(err <= 1e-9)
+
+
+def test_loop_feeds_the_projected_command_to_the_surrogate():
+    B, T = 40, 30
+    x0, ref = infeasible_starts(B, T)
+    in_scale, out_scale = np.append(OUT_MAXABS, 0.3), OUT_MAXABS
+    sim = lstm_model(load_weights("ref"))
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS)
+    fr = fca.FeasibilityRecovery()
+    res, res_lstm = cl.loop(t(x0), t(ref), sim, {"input": in_scale, "output": out_scale}, feasibility=fr)
+    x, u, info = cl.run(t(x0), t(ref), feasibility=fr)
+    assert set(res) == {"y", "y_dot", "p1", "p2", "z", "ref", "u", "u_nn", "feas_flag"}
+    assert res["u_nn"].shape == res["feas_flag"].shape == (B, T) and res["feas_flag"].dtype == torch.int32
+    assert torch.equal(res["u"], u) and torch.equal(res["u_nn"], info["u_nn"]) and torch.equal(res["feas_flag"], info["flag"])
+    assert torch.all(info["flag"][:, 0] == 1) and not torch.equal(u, info["u_nn"])
+    # the shadow track of Functions.py:1196-1231 on the PROJECTED commands
+    t_in, t_out = t(in_scale), t(out_scale)
+    for cmd_src, same in ((u, True), (info["u_nn"], False)):
+        row0 = (torch.cat([x[:, 0, 1:5], cmd_src[:, :1]], dim=1) / t_in).to(torch.float32)
+        xhat = fca.simulate_rollout(sim, row0[:, None, :].expand(B, 10, 5).contiguous(),
+                                    (cmd_src / t_in[4]).to(torch.float32), gain=out_scale / in_scale[:4])
+        track = xhat.to(torch.float64) * t_out
+        for i, k in enumerate(("y_dot", "p1", "p2", "z")):
+            assert res_lstm[k].shape == (B, T + 1)
+            assert torch.equal(res_lstm[k][:, 1:], track[:, :, i]) == same, (k, same)
