@@ -19,7 +19,8 @@ _IN_TREE = os.path.join(_HERE, "lib", _LIB_NAME)
 LIB_PATH = os.environ.get("FCR_LIB") or _IN_TREE
 
 FCR_OK = 0
-# 8: fcr_feasibility + fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag (NULL = off)
+# 8: fcr_feasibility + fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag (NULL = off).
+# fcr_supervised + fcr_supervised_epoch are a pure addition to it (no existing call or struct changed), so the number stays.
 ABI_VERSION = 8
 PRECISION_FP32, PRECISION_F16 = 0, 1
 ERRORS = {-1: "FCR_EINVAL", -2: "FCR_EWORKSPACE", -3: "FCR_EHIP", -4: "FCR_EUNSUPPORTED"}
@@ -31,7 +32,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_get_small_batch_limit", "fcr_set_small_pipe_limit", "fcr_get_small_pipe_limit", "fcr_set_small_pipe_sets",
            "fcr_get_small_pipe_sets", "fcr_set_wide_keep_budget", "fcr_get_wide_keep_budget", "fcr_last_error",
            "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
-           "fcr_lstm_rollout", "fcr_feasibility_project")
+           "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch")
+LOSS_L1, LOSS_MSE = 0, 1
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
 
@@ -102,6 +104,21 @@ class FcrClosedLoop(ctypes.Structure):
     ]
 
 
+class FcrSupervised(ctypes.Structure):
+    """fcr_supervised (include/fcr.h): one epoch of the supervised baseline for n_models stacked FNNModels."""
+    _fields_ = [
+        ("n_models", ctypes.c_int32), ("n_samples", ctypes.c_int32), ("batch_size", ctypes.c_int32),
+        ("hidden", ctypes.c_int32), ("loss_kind", ctypes.c_int32), ("train", ctypes.c_int32),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+        ("weight_decay", ctypes.c_double),
+        ("X", ctypes.c_void_p), ("y", ctypes.c_void_p), ("perm", ctypes.c_void_p),           # (n,3), (n), (M,n) int32
+        ("w_inp", ctypes.c_void_p), ("b_inp", ctypes.c_void_p), ("w_out", ctypes.c_void_p),  # (M,hidden,3), (M,hidden) x 2
+        ("exp_avg_w_inp", ctypes.c_void_p), ("exp_avg_b_inp", ctypes.c_void_p), ("exp_avg_w_out", ctypes.c_void_p),
+        ("exp_avg_sq_w_inp", ctypes.c_void_p), ("exp_avg_sq_b_inp", ctypes.c_void_p), ("exp_avg_sq_w_out", ctypes.c_void_p),
+        ("step", ctypes.c_void_p), ("loss", ctypes.c_void_p),                                # (M) fp32, (M, n_batches)
+    ]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -155,6 +172,8 @@ def load() -> ctypes.CDLL:
         lib.fcr_closed_loop_run.restype = i32
         lib.fcr_feasibility_project.argtypes = [ctypes.POINTER(FcrFeasibility), i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_feasibility_project.restype = i32
+        lib.fcr_supervised_epoch.argtypes = [ctypes.POINTER(FcrSupervised), vp]
+        lib.fcr_supervised_epoch.restype = i32
         lib.fcr_window_gather.argtypes = [ctypes.POINTER(FcrWindows), i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_window_gather.restype = i32
         lib.fcr_fnn_workspace_size.argtypes = [i32, i32, ctypes.POINTER(sz)]

@@ -1,6 +1,6 @@
 // fcr_rows.hip — C ABI of the SURVEY.md §8(f) rows that need no rollout state: the batched press plant
 // (fcr_plant.h), the controller + press closed loop (fcr_closed_loop.h), its feasibility recovery
-// (fcr_feasibility.h) and the training-window gather (fcr_window.h). Validation before any device call; stream-ordered launches; no allocation.
+// (fcr_feasibility.h), the training-window gather (fcr_window.h) and the supervised baseline's epoch (fcr_supervised.h). Validation before any device call; stream-ordered launches; no allocation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -9,6 +9,7 @@
 #include "fcr_feasibility.h"
 #include "fcr_host.h"
 #include "fcr_plant.h"
+#include "fcr_supervised.h"
 #include "fcr_window.h"
 
 using namespace fcr;
@@ -158,6 +159,47 @@ int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x
     hipLaunchKernelGGL(feasibility::feasibility_project_kernel, dim3((B + feasibility::kFeasBlock - 1) / feasibility::kFeasBlock),
                        dim3(feasibility::kFeasBlock), 0, (hipStream_t)stream, fa, B, x, u_nn, u, flag, v);
     return launch_check("feasibility_project_kernel");
+}
+
+int fcr_supervised_epoch(const fcr_supervised *c, void *stream) {
+    if (!c) return fail(FCR_EINVAL, "fcr_supervised_epoch: args is NULL");
+    if (c->n_models < 0) return fail(FCR_EINVAL, "fcr_supervised_epoch: n_models=%d must be >= 0", c->n_models);
+    if (c->n_samples < 1 || c->n_samples > (1 << 30))
+        return fail(FCR_EINVAL, "fcr_supervised_epoch: n_samples=%d must be 1..2^30", c->n_samples);
+    if (c->batch_size < 1) return fail(FCR_EINVAL, "fcr_supervised_epoch: batch_size=%d must be >= 1", c->batch_size);
+    if (c->hidden < 1 || c->hidden > fnn::kFnnMaxHidden)
+        return fail(FCR_EUNSUPPORTED, "fcr_supervised_epoch: hidden=%d: built for 1..%d", c->hidden, fnn::kFnnMaxHidden);
+    if (c->loss_kind != FCR_LOSS_L1 && c->loss_kind != FCR_LOSS_MSE)
+        return fail(FCR_EINVAL, "fcr_supervised_epoch: loss_kind=%d must be FCR_LOSS_L1 or FCR_LOSS_MSE", c->loss_kind);
+    if (c->train != 0 && c->train != 1) return fail(FCR_EINVAL, "fcr_supervised_epoch: train=%d must be 0 or 1", c->train);
+    if (c->train) {
+        if (!(c->lr >= 0.0) || !(c->eps >= 0.0) || !(c->weight_decay >= 0.0) || !(c->beta1 >= 0.0 && c->beta1 < 1.0) ||
+            !(c->beta2 >= 0.0 && c->beta2 < 1.0))
+            return fail(FCR_EINVAL, "fcr_supervised_epoch: AdamW needs lr, eps, weight_decay >= 0 and betas in [0, 1)");
+    }
+    if (c->n_models == 0) return FCR_OK;
+    if (!c->X || !c->y || !c->w_inp || !c->b_inp || !c->w_out || !c->loss)
+        return fail(FCR_EINVAL, "fcr_supervised_epoch: a required pointer is NULL");
+    if (c->train && !c->perm) return fail(FCR_EINVAL, "fcr_supervised_epoch: perm is NULL with train set");
+    if (c->train && (!c->exp_avg_w_inp || !c->exp_avg_b_inp || !c->exp_avg_w_out || !c->exp_avg_sq_w_inp ||
+                     !c->exp_avg_sq_b_inp || !c->exp_avg_sq_w_out || !c->step))
+        return fail(FCR_EINVAL, "fcr_supervised_epoch: a moment or step pointer is NULL with train set");
+    const int nb = (int)(((long long)c->n_samples + c->batch_size - 1) / c->batch_size);
+    supervised::SlArgs a{c->n_samples, c->batch_size, nb, c->hidden, c->lr, c->beta1, c->beta2,
+                         (float)(1.0 - c->lr * c->weight_decay), (float)c->eps, c->X, c->y, c->perm,
+                         c->w_inp, c->b_inp, c->w_out, c->exp_avg_w_inp, c->exp_avg_b_inp, c->exp_avg_w_out,
+                         c->exp_avg_sq_w_inp, c->exp_avg_sq_b_inp, c->exp_avg_sq_w_out, c->step, c->loss};
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(c->n_models), block(supervised::kSlBlock);
+    if (c->train && c->loss_kind == FCR_LOSS_L1)
+        hipLaunchKernelGGL((supervised::sl_epoch_kernel<supervised::kLossL1, true>), grid, block, 0, s, a);
+    else if (c->train)
+        hipLaunchKernelGGL((supervised::sl_epoch_kernel<supervised::kLossMse, true>), grid, block, 0, s, a);
+    else if (c->loss_kind == FCR_LOSS_L1)
+        hipLaunchKernelGGL((supervised::sl_epoch_kernel<supervised::kLossL1, false>), grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL((supervised::sl_epoch_kernel<supervised::kLossMse, false>), grid, block, 0, s, a);
+    return launch_check("sl_epoch_kernel");
 }
 
 }  // extern "C"

@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define FCR_ABI_VERSION 8   /* 8: fcr_feasibility, fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag */
+#define FCR_ABI_VERSION 8   /* 8: fcr_feasibility, fcr_feasibility_project; fcr_closed_loop gains feasibility / u_nn / feas_flag;
+                              * fcr_supervised_epoch joined later as a pure addition (no existing call or struct changed): look the symbol up */
 
 enum {
     FCR_OK = 0,
@@ -375,6 +376,43 @@ int fcr_wide_bwd_cell_workspace(int32_t B, int32_t H, int32_t layer0, size_t *by
 int fcr_wide_bwd_cell(int32_t B, int32_t H, int32_t layer0, const float *w_ih, const float *w_hh, const float *act,
                       const float *c_prev, const float *dh, const float *din, const float *dc, float *out,
                       float *dc_out, float *rowg, void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * One epoch of the supervised baseline (Supervised Learning/Functions.py:396-464: NeuralNetwork.train_model and
+ * validate_model) for n_models independent 3 -> hidden -> 1 FNNModels (SL/Main.py:143-159) over one sample table, in
+ * ONE launch: one workgroup per model keeps its parameters, AdamW moments and step counter on the chip and walks the
+ * batches in order (csrc/fcr_supervised.h). Batch j is rows perm[m, j*batch_size : min((j+1)*batch_size, n_samples)]
+ * of (X, y), so the last batch may be short and is averaged over its own size (DataLoader(drop_last=False) with a
+ * mean-reduced loss). Per batch: out = Hardtanh(w_out . ReLU(w_inp x + b_inp)); loss[m, j] = mean |out - y|
+ * (FCR_LOSS_L1, nn.L1Loss) or mean (out - y)^2 (FCR_LOSS_MSE, nn.MSELoss); with train != 0 its autograd gradient
+ * (sign(0) = 0, Hardtanh' = 1 on the open interval, ReLU'(0) = 0) and one torch.optim.AdamW step (decoupled decay
+ * p *= 1 - lr*weight_decay, bias-corrected moments, eps outside the square root, no amsgrad). Parameters, moments and
+ * step are updated IN PLACE when the launch ends; with train == 0 only `loss` is written. Sums run in a fixed order:
+ * the same call twice gives the same bits. No workspace. n_models = 0 is a no-op.
+ * The entries of perm must lie in [0, n_samples): the caller checks them (the kernel clamps what it reads).
+ */
+#define FCR_LOSS_L1 0
+#define FCR_LOSS_MSE 1
+typedef struct fcr_supervised {
+    int32_t n_models;     /* independent models, one workgroup each                                   */
+    int32_t n_samples;    /* rows of X and y, 1 .. 2^30                                                */
+    int32_t batch_size;   /* >= 1; any size (the lanes loop over a batch larger than the workgroup)    */
+    int32_t hidden;       /* 1 .. 64                                                                   */
+    int32_t loss_kind;    /* FCR_LOSS_L1 or FCR_LOSS_MSE                                               */
+    int32_t train;        /* 0: losses only (validate_model); 1: gradient + AdamW step per batch       */
+    double lr, beta1, beta2, eps, weight_decay;   /* torch.optim.AdamW's (read with train != 0)        */
+    const float *X;       /* (n_samples, 3)                                                            */
+    const float *y;       /* (n_samples)                                                               */
+    const int32_t *perm;  /* (n_models, n_samples) sample order per model; NULL with train == 0: 0..n-1 */
+    float *w_inp;         /* (n_models, hidden, 3)  fc_inp.weight of every model                       */
+    float *b_inp;         /* (n_models, hidden)     fc_inp.bias                                        */
+    float *w_out;         /* (n_models, hidden)     fc_out.weight                                      */
+    float *exp_avg_w_inp, *exp_avg_b_inp, *exp_avg_w_out;            /* AdamW exp_avg, shapes as above; train only   */
+    float *exp_avg_sq_w_inp, *exp_avg_sq_b_inp, *exp_avg_sq_w_out;   /* AdamW exp_avg_sq;                train only   */
+    float *step;          /* (n_models) optimizer steps taken so far, as torch keeps them (fp32); train only */
+    float *loss;          /* (n_models, ceil(n_samples / batch_size)) per-batch losses, overwritten    */
+} fcr_supervised;
+int fcr_supervised_epoch(const fcr_supervised *args, void *stream);
 
 /* Thread-local description of the last error (never NULL). */
 const char *fcr_last_error(void);
