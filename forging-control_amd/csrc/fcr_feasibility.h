@@ -143,80 +143,28 @@ __global__ __launch_bounds__(kFeasBlock) void feasibility_project_kernel(FeasArg
     if (v) v[b] = r.v;
 }
 
-// closed_loop_kernel / closed_loop_noise_kernel (fcr_closed_loop.h) with the projection between the controller and
-// the press: per step the controller exactly as there, the projection on the state the controller reads, the plant
-// step with the projected command. The reference hands NN_make_step make_step's return value (Functions.py:1170),
-// the noisy record under meas_noise, so NOISE carries all five measured components m, not only y_dot and z. The
-// projection's own model has no noise, is always the non-smooth one and has its own step (FeasArgs).
+// The command policy of the loop with recovery (closed_loop::loop_body): the projection of the controller's command
+// from the record the controller read, between the controller and the press. Stores u_nn, u and flag. The projection's
+// own model has no noise, is always the non-smooth one and has its own step (FeasArgs).
+struct ProjectedCommand {
+    FeasArgs f;
+    double *u, *u_nn;
+    int32_t *flag;
+    __device__ __forceinline__ ProjectedCommand row(size_t r) const { return {f, u + r, u_nn + r, flag + r}; }
+    __device__ __forceinline__ double operator()(const double (&m)[5], double un, int t) const {
+        const Projected r = project(m, un, f);
+        u_nn[t] = un;
+        u[t] = r.u;
+        flag[t] = r.flag;
+        return r.u;
+    }
+};
+
 template <bool SMOOTH, bool NOISE>
 __global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_recover_kernel(closed_loop::ClArgs a, FeasArgs f,
                                                                                     const double *wn, const double *vn,
                                                                                     double *u_nn, int32_t *flag) {
-    constexpr int kClBlock = closed_loop::kClBlock;
-    __shared__ float w[closed_loop::kClMaxHidden * 5];        // [j] = (w_inp[j][0..2], b_inp[j], w_out[j])
-    for (int i = threadIdx.x; i < a.hidden; i += kClBlock) {
-        w[i * 5 + 0] = a.w_inp[i * 3 + 0];
-        w[i * 5 + 1] = a.w_inp[i * 3 + 1];
-        w[i * 5 + 2] = a.w_inp[i * 3 + 2];
-        w[i * 5 + 3] = a.b_inp[i];
-        w[i * 5 + 4] = a.w_out[i];
-    }
-    __syncthreads();
-    const int b = blockIdx.x * kClBlock + threadIdx.x;
-    if (b >= a.B) return;
-    double x[5], m[5];                            // the press's state; the record the controller and the projection read
-    double *o = a.x + (size_t)b * (a.T + 1) * 5;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        x[i] = a.x0[(size_t)b * 5 + i];
-        m[i] = x[i];
-        o[i] = x[i];
-    }
-    const double *rb = a.ref + (size_t)b * a.T;
-    double *ub = a.u + (size_t)b * a.T, *nb = u_nn + (size_t)b * a.T;
-    int32_t *fb = flag + (size_t)b * a.T;
-    for (int t = 0; t < a.T; ++t) {
-        const float s0 = (float)(m[1] / a.in_scale0), s1 = (float)(m[4] / a.in_scale1), s2 = (float)(rb[t] / a.ref_scale);
-        float v = 0.0f;
-        for (int j = 0; j < a.hidden; ++j) {
-            const float *wj = w + j * 5;
-            float z = fmaf(wj[2], s2, fmaf(wj[1], s1, fmaf(wj[0], s0, wj[3])));
-            z = z > 0.0f ? z : 0.0f;
-            v = fmaf(wj[4], z, v);
-        }
-        v = fminf(fmaxf(v, -1.0f), 1.0f);
-        const double un = (double)(v * (float)a.out_scale);
-        const Projected r = project(m, un, f);
-        nb[t] = un;
-        ub[t] = r.u;
-        fb[t] = r.flag;
-        o += 5;
-        if (NOISE) {
-            double wt[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, vt[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            const size_t nt = ((size_t)b * a.T + t) * 5;
-            if (wn) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i) wt[i] = wn[nt + i];
-            }
-            if (vn) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i) vt[i] = vn[nt + i];
-            }
-            plant::rk4_step<SMOOTH>(x, r.u, a.dt, a.substeps, wt);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                m[i] = x[i] + vt[i];
-                o[i] = m[i];
-            }
-        } else {
-            plant::rk4_step<SMOOTH>(x, r.u, a.dt, a.substeps);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                m[i] = x[i];
-                o[i] = x[i];
-            }
-        }
-    }
+    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand{f, a.u, u_nn, flag});
 }
 
 }  // namespace feasibility

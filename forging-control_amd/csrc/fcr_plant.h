@@ -79,54 +79,40 @@ __device__ __forceinline__ void forging_rhs(const double (&x)[5], double u, doub
 }
 
 // One TS step of Ruge_Kuta (Functions.py:1758-1776): `substeps` RK4 stages of dt = TS/substeps.
-template <bool SMOOTH>
-__device__ __forceinline__ void rk4_step(double (&x)[5], double u, double dt, int substeps) {
-    for (int m = 0; m < substeps; ++m) {
-        double k1[5], k2[5], k3[5], k4[5], xs[5];
-        forging_rhs<SMOOTH>(x, u, k1);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = x[i] + dt / 2 * k1[i];
-        forging_rhs<SMOOTH>(xs, u, k2);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = x[i] + dt / 2 * k2[i];
-        forging_rhs<SMOOTH>(xs, u, k3);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = x[i] + dt * k3[i];
-        forging_rhs<SMOOTH>(xs, u, k4);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) x[i] = x[i] + dt / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
-    }
-}
-
-// The same step under process noise w in the units of xdot: do-mpc adds the w of a `process_noise=True` state to its
-// right-hand side (template_model.py:145-149) and the harness holds one draw over the whole sampling step
+// NOISE: the step under process noise w[5] in the units of xdot: do-mpc adds the w of a `process_noise=True` state to
+// its right-hand side (template_model.py:145-149) and the harness holds one draw over the whole sampling step
 // (Functions.py:1176-1183), so EVERY stage of every sub-step evaluates k = f(x, u) + w (not x + TS·w after the step).
 // w is constant over the step, so its share of each stage state and of the update is a term of its own —
 // x + c (f + w) = (x + c f) + c w, and dt/6 (6 w) = dt w — added AFTER the expressions of the noise-free step: with
-// w = 0 every one of them, however the compiler contracts it, is followed by + 0, and the step is the one above bit
-// for bit. An overload, so the noise-free callers keep their code.
-template <bool SMOOTH>
-__device__ __forceinline__ void rk4_step(double (&x)[5], double u, double dt, int substeps, const double (&w)[5]) {
-    double hw[5], dw[5];
+// w = 0 every one of them, however the compiler contracts it, is followed by + 0, and the step is the noise-free one
+// bit for bit (plus_noise: that trailing term). Without NOISE w is not read.
+template <bool NOISE>
+__device__ __forceinline__ double plus_noise(double a, double cw) { return NOISE ? a + cw : a; }
+
+template <bool SMOOTH, bool NOISE = false>
+__device__ __forceinline__ void rk4_step(double (&x)[5], double u, double dt, int substeps, const double *w = nullptr) {
+    double hw[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, dw[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (NOISE) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        hw[i] = dt / 2 * w[i];
-        dw[i] = dt * w[i];
+        for (int i = 0; i < 5; ++i) {
+            hw[i] = dt / 2 * w[i];
+            dw[i] = dt * w[i];
+        }
     }
     for (int m = 0; m < substeps; ++m) {
         double k1[5], k2[5], k3[5], k4[5], xs[5];
         forging_rhs<SMOOTH>(x, u, k1);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt / 2 * k1[i]) + hw[i];
+        for (int i = 0; i < 5; ++i) xs[i] = plus_noise<NOISE>(x[i] + dt / 2 * k1[i], hw[i]);
         forging_rhs<SMOOTH>(xs, u, k2);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt / 2 * k2[i]) + hw[i];
+        for (int i = 0; i < 5; ++i) xs[i] = plus_noise<NOISE>(x[i] + dt / 2 * k2[i], hw[i]);
         forging_rhs<SMOOTH>(xs, u, k3);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) xs[i] = (x[i] + dt * k3[i]) + dw[i];
+        for (int i = 0; i < 5; ++i) xs[i] = plus_noise<NOISE>(x[i] + dt * k3[i], dw[i]);
         forging_rhs<SMOOTH>(xs, u, k4);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) x[i] = (x[i] + dt / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i])) + dw[i];
+        for (int i = 0; i < 5; ++i) x[i] = plus_noise<NOISE>(x[i] + dt / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]), dw[i]);
     }
 }
 

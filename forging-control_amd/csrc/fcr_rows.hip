@@ -16,13 +16,19 @@ using namespace fcr;
 
 namespace {
 
+// ts / substeps of an RK4 integrator (what: "" or the name of whose they are), or a message
+int check_step(const char *who, const char *what, double ts, int substeps) {
+    if (substeps < 1 || substeps > 4096) return fail(FCR_EINVAL, "%s: %ssubsteps=%d must be 1..4096", who, what, substeps);
+    if (!(ts > 0.0) || ts > 1e6) return fail(FCR_EINVAL, "%s: %sts=%g must be a positive time step", who, what, ts);
+    return FCR_OK;
+}
+
 // fcr_feasibility -> the kernels' arguments (bounds scaled as the reference's NLP scales them), or a message
 int feasibility_args(const char *who, const fcr_feasibility *f, feasibility::FeasArgs *out) {
     if (!(f->p1_lo < f->p1_hi)) return fail(FCR_EINVAL, "%s: p1 bounds lo=%g must be < hi=%g", who, f->p1_lo, f->p1_hi);
     if (!(f->p2_lo < f->p2_hi)) return fail(FCR_EINVAL, "%s: p2 bounds lo=%g must be < hi=%g", who, f->p2_lo, f->p2_hi);
     if (!(f->u_lo < f->u_hi)) return fail(FCR_EINVAL, "%s: u_lo=%g must be < u_hi=%g", who, f->u_lo, f->u_hi);
-    if (f->substeps < 1 || f->substeps > 4096) return fail(FCR_EINVAL, "%s: feasibility substeps=%d must be 1..4096", who, f->substeps);
-    if (!(f->ts > 0.0) || f->ts > 1e6) return fail(FCR_EINVAL, "%s: feasibility ts=%g must be a positive time step", who, f->ts);
+    if (const int rc = check_step(who, "feasibility ", f->ts, f->substeps)) return rc;
     if (f->expand < 1 || f->expand > 20) return fail(FCR_EINVAL, "%s: expand=%d must be 1..20", who, f->expand);
     if (f->bisect < 1 || f->bisect > 60) return fail(FCR_EINVAL, "%s: bisect=%d must be 1..60", who, f->bisect);
     *out = feasibility::FeasArgs{f->p1_lo * feasibility::kPScale, f->p1_hi * feasibility::kPScale,
@@ -38,8 +44,7 @@ extern "C" {
 int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x0,
                   const double *u, double *x, void *stream) {
     if (B < 0 || S < 0) return fail(FCR_EINVAL, "fcr_plant_rk4: B=%d, S=%d must be >= 0", B, S);
-    if (substeps < 1 || substeps > 4096) return fail(FCR_EINVAL, "fcr_plant_rk4: substeps=%d must be 1..4096", substeps);
-    if (!(ts > 0.0) || ts > 1e6) return fail(FCR_EINVAL, "fcr_plant_rk4: ts=%g must be a positive time step", ts);
+    if (const int rc = check_step("fcr_plant_rk4", "", ts, substeps)) return rc;
     if (smooth != 0 && smooth != 1) return fail(FCR_EINVAL, "fcr_plant_rk4: smooth=%d must be 0 or 1", smooth);
     if ((long long)B * (S + 1) * 5 > (1LL << 40)) return fail(FCR_EINVAL, "fcr_plant_rk4: B*(S+1) too large");
     if (B == 0) return FCR_OK;
@@ -49,10 +54,8 @@ int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smo
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((B + plant::kPlantBlock - 1) / plant::kPlantBlock);
     const double dt = ts / substeps;
-    if (smooth)
-        hipLaunchKernelGGL(plant::plant_rk4_kernel<true>, grid, dim3(plant::kPlantBlock), 0, s, B, S, dt, substeps, x0, u, x);
-    else
-        hipLaunchKernelGGL(plant::plant_rk4_kernel<false>, grid, dim3(plant::kPlantBlock), 0, s, B, S, dt, substeps, x0, u, x);
+    hipLaunchKernelGGL(smooth ? plant::plant_rk4_kernel<true> : plant::plant_rk4_kernel<false>, grid,
+                       dim3(plant::kPlantBlock), 0, s, B, S, dt, substeps, x0, u, x);
     return launch_check("plant_rk4_kernel");
 }
 
@@ -85,8 +88,7 @@ int fcr_window_gather(const fcr_windows *t, int32_t B, const int64_t *idx, float
 int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
     if (!c) return fail(FCR_EINVAL, "fcr_closed_loop_run: args is NULL");
     if (c->B < 0 || c->T < 0) return fail(FCR_EINVAL, "fcr_closed_loop_run: B=%d, T=%d must be >= 0", c->B, c->T);
-    if (c->substeps < 1 || c->substeps > 4096) return fail(FCR_EINVAL, "fcr_closed_loop_run: substeps=%d must be 1..4096", c->substeps);
-    if (!(c->ts > 0.0) || c->ts > 1e6) return fail(FCR_EINVAL, "fcr_closed_loop_run: ts=%g must be a positive time step", c->ts);
+    if (const int rc = check_step("fcr_closed_loop_run", "", c->ts, c->substeps)) return rc;
     if (c->smooth != 0 && c->smooth != 1) return fail(FCR_EINVAL, "fcr_closed_loop_run: smooth=%d must be 0 or 1", c->smooth);
     if (c->ctrl_hidden < 1 || c->ctrl_hidden > closed_loop::kClMaxHidden)
         return fail(FCR_EUNSUPPORTED, "fcr_closed_loop_run: ctrl_hidden=%d: built for 1..%d", c->ctrl_hidden,
@@ -113,37 +115,23 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
                           c->ref_scale, c->out_scale, c->x, c->u};
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((c->B + closed_loop::kClBlock - 1) / closed_loop::kClBlock);
-    if (c->T > 0 && c->feasibility) {                        // recovery between controller and press: kernels of their own
-        const dim3 block(closed_loop::kClBlock);
-        const bool noise = c->process_noise || c->meas_noise;
-        if (c->smooth && noise)
-            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<true, true>), grid, block, 0, s, a, fa,
-                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
-        else if (c->smooth)
-            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<true, false>), grid, block, 0, s, a, fa,
-                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
-        else if (noise)
-            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<false, true>), grid, block, 0, s, a, fa,
-                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
-        else
-            hipLaunchKernelGGL((feasibility::closed_loop_recover_kernel<false, false>), grid, block, 0, s, a, fa,
-                               c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
-        return launch_check("closed_loop_recover_kernel");
+    const dim3 block(closed_loop::kClBlock);
+    // one loop (closed_loop::loop_body), instantiated per [smooth] and, with recovery, [noise]; T = 0 only copies x0
+    const bool sm = c->smooth, noise = c->T > 0 && (c->process_noise || c->meas_noise), recover = c->T > 0 && c->feasibility;
+    if (recover) {
+        using feasibility::closed_loop_recover_kernel;
+        static constexpr decltype(&closed_loop_recover_kernel<false, false>) k[2][2] = {
+            {closed_loop_recover_kernel<false, false>, closed_loop_recover_kernel<false, true>},
+            {closed_loop_recover_kernel<true, false>, closed_loop_recover_kernel<true, true>}};
+        hipLaunchKernelGGL(k[sm][noise], grid, block, 0, s, a, fa, c->process_noise, c->meas_noise, c->u_nn, c->feas_flag);
+    } else if (noise) {
+        hipLaunchKernelGGL(sm ? closed_loop::closed_loop_noise_kernel<true> : closed_loop::closed_loop_noise_kernel<false>,
+                           grid, block, 0, s, a, c->process_noise, c->meas_noise);
+    } else {
+        hipLaunchKernelGGL(sm ? closed_loop::closed_loop_kernel<true> : closed_loop::closed_loop_kernel<false>, grid, block,
+                           0, s, a);
     }
-    if (c->T > 0 && (c->process_noise || c->meas_noise)) {   // the harness's noise: a kernel of its own
-        if (c->smooth)
-            hipLaunchKernelGGL(closed_loop::closed_loop_noise_kernel<true>, grid, dim3(closed_loop::kClBlock), 0, s, a,
-                               c->process_noise, c->meas_noise);
-        else
-            hipLaunchKernelGGL(closed_loop::closed_loop_noise_kernel<false>, grid, dim3(closed_loop::kClBlock), 0, s, a,
-                               c->process_noise, c->meas_noise);
-        return launch_check("closed_loop_noise_kernel");
-    }
-    if (c->smooth)
-        hipLaunchKernelGGL(closed_loop::closed_loop_kernel<true>, grid, dim3(closed_loop::kClBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL(closed_loop::closed_loop_kernel<false>, grid, dim3(closed_loop::kClBlock), 0, s, a);
-    return launch_check("closed_loop_kernel");
+    return launch_check(recover ? "closed_loop_recover_kernel" : (noise ? "closed_loop_noise_kernel" : "closed_loop_kernel"));
 }
 
 int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,

@@ -1,6 +1,7 @@
 """NumPy restatement of the batched closed loop (TEST INFRASTRUCTURE ONLY).
 
-Per step, as NeuralNetwork.loop (Functions.py:1116-1200) without feasibility recovery and noise:
+Per step, as NeuralNetwork.loop (Functions.py:1116-1200), with the harness's pre-drawn noise and a projection of the
+command (its feasibility recovery) as options:
 NN_make_step (Functions.py:1594-1604) — MaxAbs-scaled [y_dot, z, ref] in fp64 (the reference column by
 scalers['y_dot']), the FNN in float32 (Linear+ReLU, Linear without bias, Hardtanh; the kernel's FMA order),
 unscaled by scalers['output'] in float32 — then the plant step of oracle/plant_np.py (RK4 of
@@ -40,15 +41,22 @@ def controller_u(x, ref, W_inp, b_inp, W_out, in_scale, ref_scale, out_scale):
     return (v * f32(out_scale)).astype(np.float64)
 
 
-def closed_loop(x0, ref, W_inp, b_inp, W_out, in_scale, ref_scale, out_scale, ts=1e-3, substeps=4, smooth=True):
-    x = np.asarray(x0, np.float64)
+def closed_loop(x0, ref, W_inp, b_inp, W_out, in_scale, ref_scale, out_scale, ts=1e-3, substeps=4, smooth=True,
+                process_noise=None, meas_noise=None, project=None):
+    """x (B,T+1,5), u (B,T). One step: the controller reads the record m = x + meas_noise[:, t-1] (x0 at t = 0), the
+    plant steps the unperturbed state x under process_noise[:, t] (rk4_step's ``w``), the new record is x[:, t+1].
+    ``project(m, x, u_nn) -> (u, flag)`` stands between the controller and the press (the harness's feasibility
+    recovery, tests/feasibility_np.py); with it the result is x, u, u_nn (B,T), flag (B,T)."""
+    x = m = np.asarray(x0, np.float64)
     B, T = ref.shape
-    xs = np.empty((B, T + 1, 5))
-    us = np.empty((B, T))
+    xs, us, un, fl = np.empty((B, T + 1, 5)), np.empty((B, T)), np.empty((B, T)), np.zeros((B, T), np.int32)
     xs[:, 0] = x
     for t in range(T):
-        u = controller_u(x, ref[:, t], W_inp, b_inp, W_out, in_scale, ref_scale, out_scale)
-        x = rk4_step(x, u, ts, substeps, smooth)
+        u = un[:, t] = controller_u(m, ref[:, t], W_inp, b_inp, W_out, in_scale, ref_scale, out_scale)
+        if project is not None:
+            u, fl[:, t] = project(m, x, u)
+        x = rk4_step(x, u, ts, substeps, smooth, None if process_noise is None else process_noise[:, t])
+        m = x if meas_noise is None else x + meas_noise[:, t]
         us[:, t] = u
-        xs[:, t + 1] = x
-    return xs, us
+        xs[:, t + 1] = m
+    return (xs, us) if project is None else (xs, us, un, fl)

@@ -89,15 +89,18 @@ def forging_rhs(x: np.ndarray, u: np.ndarray, smooth: bool = False) -> np.ndarra
     ], axis=-1)
 
 
-def rk4_step(x, u, ts: float = 1e-3, substeps: int = 4, smooth: bool = False) -> np.ndarray:
-    """F(x0, u) of Functions.py:1758-1779: `substeps` RK4 steps of ts/substeps, u held."""
+def rk4_step(x, u, ts: float = 1e-3, substeps: int = 4, smooth: bool = False, w=None) -> np.ndarray:
+    """F(x0, u) of Functions.py:1758-1779: `substeps` RK4 steps of ts/substeps, u held. ``w`` (..., 5): process noise
+    in the units of xdot, held over the step: every stage evaluates f(x, u) + w (do-mpc adds a process_noise state's w
+    to the right-hand side, template_model.py:145-149; the harness holds one draw per step, Functions.py:1176-1183)."""
     dt = ts / substeps
     x = np.asarray(x, np.float64)
+    f = (lambda xs: forging_rhs(xs, u, smooth)) if w is None else (lambda xs: forging_rhs(xs, u, smooth) + w)
     for _ in range(substeps):
-        k1 = forging_rhs(x, u, smooth)
-        k2 = forging_rhs(x + dt / 2 * k1, u, smooth)
-        k3 = forging_rhs(x + dt / 2 * k2, u, smooth)
-        k4 = forging_rhs(x + dt * k3, u, smooth)
+        k1 = f(x)
+        k2 = f(x + dt / 2 * k1)
+        k3 = f(x + dt / 2 * k2)
+        k4 = f(x + dt * k3)
         x = x + dt / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
     return x
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from oracle.closed_loop_np import closed_loop
 from oracle.plant_np import rk4_step
 
 P_SCALE = 1 / 32e6                      # scaling_factors['p1'] = scaling_factors['p2'], UL/Main.py:607-608
@@ -95,30 +96,7 @@ def closed_loop_recover(x0, ref, W_inp, b_inp, W_out, in_scale, ref_scale, out_s
     record only). ``project_reads_record=False`` is the WRONG loop a test sets beside the right one: its projection
     sees the noisy y_dot and z the controller reads but the press's own y, p1, p2. Returns x (B,T+1,5), u (B,T),
     u_nn (B,T), flag (B,T)."""
-    from oracle.closed_loop_np import controller_u
-    from oracle.plant_np import forging_rhs
-
     feas = dict(feas or {})
-    x = np.asarray(x0, np.float64)
-    B, T = ref.shape
-    xs, us, un, fl = np.empty((B, T + 1, 5)), np.empty((B, T)), np.empty((B, T)), np.empty((B, T), np.int32)
-    xs[:, 0] = x
-    m = x
-    dt = ts / substeps
-    for t in range(T):
-        u_nn = controller_u(m, ref[:, t], W_inp, b_inp, W_out, in_scale, ref_scale, out_scale)
-        u, flag, _ = project(m if project_reads_record else np.stack([x[:, 0], m[:, 1], x[:, 2], x[:, 3], m[:, 4]], 1),
-                             u_nn, **feas)
-        if process_noise is None:
-            x = rk4_step(x, u, ts, substeps, smooth)
-        else:
-            w = process_noise[:, t]
-            for _ in range(substeps):
-                k1 = forging_rhs(x, u, smooth) + w
-                k2 = forging_rhs(x + dt / 2 * k1, u, smooth) + w
-                k3 = forging_rhs(x + dt / 2 * k2, u, smooth) + w
-                k4 = forging_rhs(x + dt * k3, u, smooth) + w
-                x = x + dt / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
-        m = x if meas_noise is None else x + meas_noise[:, t]
-        us[:, t], un[:, t], fl[:, t], xs[:, t + 1] = u, u_nn, flag, m
-    return xs, us, un, fl
+    seen = (lambda m, x: m) if project_reads_record else (lambda m, x: np.stack([x[:, 0], m[:, 1], x[:, 2], x[:, 3], m[:, 4]], 1))
+    return closed_loop(x0, ref, W_inp, b_inp, W_out, in_scale, ref_scale, out_scale, ts, substeps, smooth, process_noise,
+                       meas_noise, project=lambda m, x, u_nn: project(seen(m, x), u_nn, **feas)[:2])

@@ -144,6 +144,25 @@ def test_noisy_smooth_loop_projects_from_the_noisy_record():
     assert np.abs(ur - uw).max() > 1e-3 * np.abs(ur).max()
 
 
+def test_noisy_nonsmooth_loop_with_recovery_matches_oracle():
+    """closed_loop_recover_kernel<false, true>: the non-smooth press under w and v with recovery (the test above runs
+    the smooth one). On the CPU the oracle flags every trajectory at step 0 and stays finite over these 40 steps."""
+    B, T = 70, 40
+    x0, ref = infeasible_starts(B, T)
+    w, v = fca.closed_loop.harness_noise(B, T, PROCESS_STD, MEAS_STD, np.random.RandomState(7))
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS, smooth=False)
+    x, u, info = cl.run(t(x0), t(ref), process_noise=t(w), meas_noise=t(v), feasibility=fca.FeasibilityRecovery())
+    xr, ur, unr, flr = oracle(x0, ref, False, w, v)
+    assert np.all(flr[:, 0] == 1) and np.isfinite(xr).all()                  # recovery acts from step 0
+    x, u, u_nn, flag = x.cpu().numpy(), u.cpu().numpy(), info["u_nn"].cpu().numpy(), info["flag"].cpu().numpy()
+    err, uerr = loop_errors(x, u, xr, ur)
+    print(f"state err {err}, u err {uerr:.3g}; flagged {np.count_nonzero(flag)} (oracle {np.count_nonzero(flr)})")
+    assert np.all(err < 1e-5), err
+    assert uerr <= 1e-5
+    assert np.array_equal(flag[:, 0], flr[:, 0])
+    assert np.abs(u_nn - unr).max() <= 1e-5 * np.abs(unr).max()
+
+
 def test_unflagged_run_is_the_plain_run():
     x0, ref = press_case()
     ref = ref[:, :20]

@@ -10,8 +10,7 @@ import torch
 
 import forging_control_amd as fca
 from conftest import GOLDEN
-from oracle.closed_loop_np import closed_loop, controller_u
-from oracle.plant_np import forging_rhs
+from oracle.closed_loop_np import closed_loop
 from oracle.rollout_np import lstm_forward
 from test_closed_loop import SCALERS, ctrl_weights
 from test_harness import OUT_MAXABS
@@ -26,29 +25,11 @@ DEV = "cuda:0"
 # ---------------------------------------------------------------------------------------------
 # the press under noise
 # ---------------------------------------------------------------------------------------------
-def noisy_loop_oracle(x0, ref, w, v, smooth, ts=1e-3, substeps=4):
-    """closed_loop_np.closed_loop with the harness's noise: every RK4 stage evaluates f(x,u) + w[:,t] (do-mpc adds
-    a process_noise state's w to the right-hand side; the draw is held over the step), the record is x + v[:,t] and
-    the controller reads the record; the integration goes on from the unperturbed state."""
-    W_inp, b_inp, W_out = ctrl_weights()
-    x = np.asarray(x0, np.float64)
-    rec = x
-    B, T = ref.shape
-    xs, us = np.empty((B, T + 1, 5)), np.empty((B, T))
-    xs[:, 0] = x
-    dt = ts / substeps
-    for t in range(T):
-        u = controller_u(rec, ref[:, t], W_inp, b_inp, W_out, SCALERS["input"][:2], SCALERS["y_dot"], SCALERS["output"])
-        for _ in range(substeps):
-            k1 = forging_rhs(x, u, smooth) + w[:, t]
-            k2 = forging_rhs(x + dt / 2 * k1, u, smooth) + w[:, t]
-            k3 = forging_rhs(x + dt / 2 * k2, u, smooth) + w[:, t]
-            k4 = forging_rhs(x + dt * k3, u, smooth) + w[:, t]
-            x = x + dt / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
-        rec = x + v[:, t]
-        us[:, t] = u
-        xs[:, t + 1] = rec
-    return xs, us
+def noisy_loop_oracle(x0, ref, w, v, smooth):
+    """closed_loop_np.closed_loop with the harness's noise: process noise w (or None) at every RK4 stage, measurement
+    noise v (or None) on the record the controller reads."""
+    return closed_loop(x0, ref, *ctrl_weights(), SCALERS["input"][:2], SCALERS["y_dot"], SCALERS["output"], smooth=smooth,
+                       process_noise=w, meas_noise=v)
 
 
 @functools.lru_cache(maxsize=None)
@@ -99,6 +80,35 @@ def test_noisy_press_matches_oracle(smooth):
         assert np.all(err < 1e-5), (name, err)
         assert uerr <= 1e-5, (name, uerr)
         assert np.all(moved > 1e-3), (name, moved)               # a kernel that ignores the noise does not pass
+
+
+@pytest.mark.parametrize("smooth", [True, False])
+def test_measurement_noise_alone_matches_oracle(smooth):
+    """process_noise=None, meas_noise=v: the first 20 steps of press_case(). MEAS_STD is small beside the states, so
+    "moved by the noise" is measured against the oracle's own two runs, not a fixed floor: on the CPU the oracle with v
+    is away from the oracle without it by [0.068, 0.096, 0.0099, 0.019, 0.027] of each state's range and 0.017 of
+    u's (both plant models, to these digits); the GPU runs must be at least half that apart."""
+    x0, ref, _, v = press_case()
+    ref, v = ref[:, :20], v[:, :20]
+    cl = fca.ClosedLoop(gpu_controller(), SCALERS, smooth=smooth)
+    t = lambda a: torch.tensor(a, device=DEV)
+    xc, uc = (a.cpu().numpy() for a in cl.run(t(x0), t(ref)))
+    x, u = (a.cpu().numpy() for a in cl.run(t(x0), t(ref), meas_noise=t(v)))
+    xrc, urc = noisy_loop_oracle(x0, ref, None, None, smooth)
+    xr, ur = noisy_loop_oracle(x0, ref, None, v, smooth)
+    assert np.isfinite(xr).all() and xr[:, :, 1].min() > -0.5
+    assert np.array_equal(x[:, 0], x0)
+    scale, uscale = np.abs(xr).reshape(-1, 5).max(0), np.abs(ur).max()
+    err = (np.abs(x - xr).reshape(-1, 5) / scale).max(0)
+    uerr = np.abs(u - ur).max() / uscale
+    moved, moved_ref = (np.abs(x - xc).reshape(-1, 5) / scale).max(0), (np.abs(xr - xrc).reshape(-1, 5) / scale).max(0)
+    umoved, umoved_ref = np.abs(u - uc).max() / uscale, np.abs(ur - urc).max() / uscale
+    print(f"smooth={smooth} v: state err {err}, u err {uerr:.3g}, moved by the noise {moved} / {umoved:.3g}, "
+          f"the oracle {moved_ref} / {umoved_ref:.3g}")
+    assert np.all(err < 1e-5), err
+    assert uerr <= 1e-5, uerr
+    assert np.all(moved_ref > 0) and umoved_ref > 0
+    assert np.all(moved >= 0.5 * moved_ref) and umoved >= 0.5 * umoved_ref   # a kernel that ignores v does not pass
 
 
 def test_noise_arguments_are_checked():
