@@ -1,6 +1,7 @@
 // fcr_bwd.h — backward of the rollout (what loss.backward(), Functions.py:655, computes for the
 // controller): reverse over windows; per window three layer phases (2 -> 1 -> 0), each reverse over
-// t = 9..0, with that layer's weight image resident in LDS (fcr_img.h).
+// t = 9..t_lo (the cells a gradient can reach: t_lo = max(0, 9 - window), fcr_bwd_kernel), with that layer's weight
+// image resident in LDS (fcr_img.h).
 //
 // Recompute, not store: each cell rebuilds its gate pre-activations from (x_t, h_{t-1}, c_{t-1}) —
 // the forward kept h and c (8 B per unit slot) — with the very products and pointwise arithmetic of
@@ -150,7 +151,8 @@ constexpr float kInvNegLog2e = 1.0f / kNegLog2e;
 // recomputed forward tiles 2kb+2, 2kb+3 and their gradients, which form block kb+1.
 // OWN: the cell's own h_t record is in ci.o (every cell but the first of a window's layer-2 phase, whose h_9
 // only fed the readout): tanh(c_t) comes from it (lstm_point_grad_h) instead of being re-evaluated.
-// NX_OWN: the next cell's is fetched. (The f16 mode's record holds f16(h) only: tanh(c_t) = h f16-rounded / o, the
+// NX_OWN: the next cell's is fetched. NX_SAME_PHASE: the next cell is t - 1 of this layer (false: the last cell of a
+// phase that ends before t = 0, fcr_bwd_kernel's reach rule). (The f16 mode's record holds f16(h) only: tanh(c_t) = h f16-rounded / o, the
 // same accuracy against the fp64 oracle as re-evaluating tanh from the c record, scripts/f16_errs.py, and 5 % faster.)
 #ifndef FCR_STAMP
 #define FCR_STAMP 0   // diagnostic: per-wave s_memtime sums of the cell's sections (ws tail)
@@ -167,7 +169,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 
 template <int HS, bool L0, bool DIN, bool FIRST, bool NX_L0, bool NX_HC, bool NX_DIN, bool LP, bool OWN = true,
-          bool NX_OWN = true, bool DG = false>
+          bool NX_OWN = true, bool DG = false, bool NX_SAME_PHASE = true>
 __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, const float (&ext)[HS],
                                          float (&dh)[HS], float (&dc)[HS], float (&dxo)[HS], float &dxq,
                                          float &dx4, CellIn<HS> &ci, const NextIn &nx, Stamps &sp,
@@ -327,8 +329,10 @@ __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, con
         if (DG) dgd = m > 0.0f ? down : 0.0f;
     }
     // OWN_REG: the next cell (t - 1, same phase) owns h_{t-1}, whose record this cell has in ci.h: kept in registers
-    // for it instead of re-read from the slab (an L2 miss by then)
-    constexpr bool OWN_REG = NX_OWNH && !FIRST;
+    // for it instead of re-read from the slab (an L2 miss by then). Not so for the last cell of a phase (FIRST, or a
+    // truncated phase's t_lo > 0: NX_SAME_PHASE = false): the next cell is t = 9 of another layer, whose own record
+    // comes from the slab (nx.o)
+    constexpr bool OWN_REG = NX_OWNH && !FIRST && NX_SAME_PHASE;
     f32x4 hkeep[Geo<HS>::HQ];
     if constexpr (OWN_REG) {
 #pragma unroll
@@ -517,10 +521,15 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
     nb.rd = wave_rsrc(a.dseq + (size_t)wave * dseq_sz, dseq_sz * 16);
     auto hoff = [&](int j, int l, int t) { return (uint32_t)(((size_t)(j * kLayers + l) * kL + t) * qcell * 16); };
     auto doff = [&](int j, int lfrom, int t) { return ((size_t)(j * 2 + (2 - lfrom)) * kL + t) * qcell; };
+    // Reach: the only window entries with a gradient are u0 (row 9 of window 0) and the appended rows (xhat_j, u_{j+1});
+    // in window j they sit at positions t_lo(j) = max(0, 9 - j) .. 9, the rows before them are the caller's `states`.
+    // A cell (l, t) sends gradient only to x_s, s <= t (the LSTM's weights are frozen), so every phase of window j
+    // stops after t = t_lo(j): 3 (j + 1) of a window's 30 cells for j < 9 (N = 10: 165 of 300).
+    auto t_lo_of = [&](int j) { return j < kL - 1 ? kL - 1 - j : 0; };
     auto next_of = [&](int j, int l, int t) {   // the cell processed after (j, l, t)
         NextIn n = nb;
         int nj = j, nl = l, nt = t - 1;
-        if (t == 0) {
+        if (t == t_lo_of(j)) {   // the phase's last cell: on to t = 9 of the layer below, or of layer 2 of window j - 1
             nt = kL - 1;
             nl = l - 1;
             if (l == 0) { nl = 2; nj = j - 1; }
@@ -602,25 +611,48 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         }
 #pragma unroll
         for (int r = 0; r < HS; ++r) dh[r] = dc[r] = 0.0f;
-        // t = 9 .. 2: the next cell is t-1 of the same layer; t = 1: the next is the FIRST cell (no
-        // h, c); t = 0: the next is t = 9 of the layer below (or of layer 2 of the previous window)
+        // Every phase runs t = 9 .. t_lo (wave-uniform). The generic cells' next cell is t-1 of the same layer, with
+        // h_{t-1}, c_{t-1}. t_lo = 0: t = 1: the next is the FIRST cell (no h, c); t = 0 (FIRST): the next is t = 9 of
+        // the layer below (or of layer 2 of the previous window). t_lo >= 1: the phase ends with a truncated-last cell,
+        // not FIRST (it recomputes from h, c of t_lo - 1; its dh_prev, dc go nowhere) with the FIRST cell's prefetch
+        // flags and its next cell's own record from the slab (NX_SAME_PHASE = false).
+        const int t_lo = t_lo_of(j);
+        const int t_gen = t_lo > 0 ? t_lo + 1 : 2;   // the generic cells run down to here
+        const bool one_cell = t_lo == kL - 1;        // window 0: every phase is its truncated-last cell alone
+        // One-cell phases prefetch the din of the layer below at t = 9 before this phase has stored it (the prefetch
+        // sits inside the cell, the store behind it): that record is fetched again behind the store.
+        auto din_again = [&](int lfrom) {
+            ld_rec<HS, din_words<HS, LP>()>(ci.d, nb.rd, (uint32_t)((doff(j, lfrom, kL - 1)) * 16), lane);
+        };
         // t = 9: h_9 of layer 2 only fed the readout (no split record), so this cell re-evaluates tanh(c_9)
-        bwd_cell<HS, false, false, false, false, true, false, LP, false>(L1.fb, L1.tb, lane, dh_out, dh, dc, dxo, unused0,
-                                                                    unused1, ci, next_of(j, 2, kL - 1), sp);
+        if (one_cell) {
+            bwd_cell<HS, false, false, false, false, true, true, LP, false, true, false, false>(
+                L1.fb, L1.tb, lane, dh_out, dh, dc, dxo, unused0, unused1, ci, next_of(j, 2, kL - 1), sp);
+        } else {
+            bwd_cell<HS, false, false, false, false, true, false, LP, false>(L1.fb, L1.tb, lane, dh_out, dh, dc, dxo, unused0,
+                                                                        unused1, ci, next_of(j, 2, kL - 1), sp);
+        }
         din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, kL - 1)) * 16), dxo, lane);
+        if (one_cell) din_again(2);
 #pragma unroll
         for (int r = 0; r < HS; ++r) dab[r] = 0.0f;
-        for (int t = kL - 2; t >= 2; --t) {
+        for (int t = kL - 2; t >= t_gen; --t) {
             bwd_cell<HS, false, false, false, false, true, false, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
                                                                 unused1, ci, next_of(j, 2, t), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, t)) * 16), dxo, lane);
         }
-        bwd_cell<HS, false, false, false, false, false, false, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
-                                                             unused1, ci, next_of(j, 2, 1), sp);
-        din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 1)) * 16), dxo, lane);
-        bwd_cell<HS, false, false, true, false, true, true, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
-                                                          unused1, ci, next_of(j, 2, 0), sp);
-        din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 0)) * 16), dxo, lane);
+        if (t_lo == 0) {
+            bwd_cell<HS, false, false, false, false, false, false, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
+                                                                 unused1, ci, next_of(j, 2, 1), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 1)) * 16), dxo, lane);
+            bwd_cell<HS, false, false, true, false, true, true, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
+                                                              unused1, ci, next_of(j, 2, 0), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 0)) * 16), dxo, lane);
+        } else if (!one_cell) {
+            bwd_cell<HS, false, false, false, false, true, true, LP, true, true, false, false>(
+                L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 2, t_lo), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, t_lo)) * 16), dxo, lane);
+        }
         // ---- layer 1 ----
         const unsigned long long tw3 = stamp_now();
         if (!LP) {
@@ -629,30 +661,42 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         if (FCR_STAMP) sp.t[7] += stamp_now() - tw3;
 #pragma unroll
         for (int r = 0; r < HS; ++r) dh[r] = dc[r] = 0.0f;
-        for (int t = kL - 1; t >= 2; --t) {
+        for (int t = kL - 1; t >= t_gen; --t) {
             bwd_cell<HS, false, true, false, false, true, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
                                                               unused1, ci, next_of(j, 1, t), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, t)) * 16), dxo, lane);
         }
-        bwd_cell<HS, false, true, false, false, false, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
-                                                           unused1, ci, next_of(j, 1, 1), sp);
-        din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 1)) * 16), dxo, lane);
-        bwd_cell<HS, false, true, true, true, true, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
-                                                        unused1, ci, next_of(j, 1, 0), sp);
-        din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 0)) * 16), dxo, lane);
+        if (t_lo == 0) {
+            bwd_cell<HS, false, true, false, false, false, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
+                                                               unused1, ci, next_of(j, 1, 1), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 1)) * 16), dxo, lane);
+            bwd_cell<HS, false, true, true, true, true, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
+                                                            unused1, ci, next_of(j, 1, 0), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 0)) * 16), dxo, lane);
+        } else {
+            bwd_cell<HS, false, true, false, true, true, true, LP, true, true, false, false>(
+                L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 1, t_lo), sp);
+            din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, t_lo)) * 16), dxo, lane);
+            if (one_cell) din_again(1);
+        }
         // ---- layer 0: dx -> window-row gradients ----
         if (!LP) {
             lds_fill<I0::BYTES, kBwdWaves>(lw, a.p.img[0]);
         }
 #pragma unroll
         for (int r = 0; r < HS; ++r) dh[r] = dc[r] = 0.0f;
-        for (int t = kL - 1; t >= 2; --t) {
+        for (int t = kL - 1; t >= t_gen; --t) {
             float dxq, dx4;
             bwd_cell<HS, true, true, false, true, true, true, LP>(L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci,
                                                             next_of(j, 0, t), sp);
             buf_st2(rr, lane * 8, (uint32_t)((j * kL + t) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row j+t
         }
-        {
+        if (t_lo > 0) {
+            float dxq, dx4;
+            bwd_cell<HS, true, true, false, false, true, false, LP, true, false, false, false>(
+                L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci, next_of(j, 0, t_lo), sp);
+            buf_st2(rr, lane * 8, (uint32_t)((j * kL + t_lo) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row 9
+        } else {
             float dxq, dx4;
             bwd_cell<HS, true, true, false, true, false, true, LP>(L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci,
                                                              next_of(j, 0, 1), sp);
