@@ -117,7 +117,10 @@ def make_case(name, params, B, N, seed, wide=False, noise=False):
     for k in grads:
         out[f"{k}_64"] = grads[k]
         out[f"{k}_32"] = t32[k].astype(np.float32)
-    # branch coverage of the fixture (printed; tests assert the stress cases hit them)
+    # coarse branch counts of the fixture (printed; test_oracle.py asserts the stress cases have some). con_active is the
+    # OR of the constraint's four branches, and u_saturated counts `prediction`, which includes u0 — computed by the
+    # caller's controller, outside the loss. Neither says that each branch, or the in-loss Hardtanh, fires: the
+    # per-branch coverage is tests/test_kink_cases.py (cases built from seeds, no fixture).
     xh = feats["xhat"]
     cover = {
         "con_active": int(((xh[..., 1] < 0) | (xh[..., 1] > R.P1_MAX) | (xh[..., 2] < 0) | (xh[..., 2] > R.P2_MAX)).sum()),

@@ -111,6 +111,38 @@ def test_measurement_noise_alone_matches_oracle(smooth):
     assert np.all(moved >= 0.5 * moved_ref) and umoved >= 0.5 * umoved_ref   # a kernel that ignores v does not pass
 
 
+@pytest.mark.parametrize("smooth", [True, False])
+def test_saturating_controller_fires_both_clamps(smooth):
+    """The controller's Hardtanh in the closed loop (fcr_closed_loop.h): on press_case() the command stays within
+    [-0.71, 0.52] of the output scale, clean and noisy, so neither clamp fires in any other test here. With W_out doubled,
+    over the 20 steps 10..29 of press_case() — the ten before and the ten after the reference changes sign — the fp64
+    oracle commands +out_scale in 6 % of the steps and -out_scale in 2 %, every state stays finite and y_dot stays above
+    -0.46 (both plant models; over the first 20 steps alone the reference is positive and the lower clamp never
+    fires, over all 40 y_dot passes -0.5). Same bounds as the tests above."""
+    x0, ref, _, _ = press_case()
+    ref = np.ascontiguousarray(ref[:, 10:30])
+    W_inp, b_inp, W_out = ctrl_weights()
+    W_out = np.float32(2) * W_out
+    ctrl = gpu_controller()
+    with torch.no_grad():
+        ctrl.fc_out.weight.copy_(torch.tensor(W_out))
+    xr, ur = closed_loop(x0, ref, W_inp, b_inp, W_out, SCALERS["input"][:2], SCALERS["y_dot"], SCALERS["output"],
+                         smooth=smooth)
+    top = float(np.float32(SCALERS["output"]))
+    hi, lo = float((ur >= top).mean()), float((ur <= -top).mean())
+    assert np.isfinite(xr).all() and xr[:, :, 1].min() > -0.5
+    assert hi >= 0.01 and lo >= 0.01, (hi, lo)                   # both clamps fire in the oracle
+    t = lambda a: torch.tensor(a, device=DEV)
+    x, u = (a.cpu().numpy() for a in fca.ClosedLoop(ctrl, SCALERS, smooth=smooth).run(t(x0), t(ref)))
+    assert np.array_equal(x[:, 0], x0)
+    scale = np.abs(xr).reshape(-1, 5).max(0)
+    err = (np.abs(x - xr).reshape(-1, 5) / scale).max(0)
+    uerr = np.abs(u - ur).max() / np.abs(ur).max()
+    print(f"smooth={smooth} W_out x 2: +clamp {hi:.3f}, -clamp {lo:.3f}, state err {err}, u err {uerr:.3g}")
+    assert np.all(err < 1e-5), err
+    assert uerr <= 1e-5, uerr
+
+
 def test_noise_arguments_are_checked():
     cl = fca.ClosedLoop(gpu_controller(), SCALERS)
     x0 = torch.zeros(4, 5, dtype=torch.float64, device=DEV)
