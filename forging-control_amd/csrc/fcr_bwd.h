@@ -1,7 +1,9 @@
 // fcr_bwd.h — backward of the rollout (what loss.backward(), Functions.py:655, computes for the
 // controller): reverse over windows; per window three layer phases (2 -> 1 -> 0), each reverse over
 // t = 9..t_lo (the cells a gradient can reach: t_lo = max(0, 9 - window), fcr_bwd_kernel), with that layer's weight
-// image resident in LDS (fcr_img.h).
+// image resident in LDS (fcr_img.h). A cell reads x_t, h_{t-1}, c_{t-1} and its own h_t, so nothing before t_lo - 1 of
+// a window is ever fetched: the forward stores no other record (fcr_fwd.h; the record contract at small_limit_of,
+// fcr_rollout.hip).
 //
 // Recompute, not store: each cell rebuilds its gate pre-activations from (x_t, h_{t-1}, c_{t-1}) —
 // the forward kept h and c (8 B per unit slot) — with the very products and pointwise arithmetic of

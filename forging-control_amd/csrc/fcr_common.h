@@ -306,6 +306,30 @@ __device__ __forceinline__ void buf_store_rec(__amdgpu_buffer_rsrc_t r, uint32_t
 // A cell's c record: fp32 per slot; in the f16 mode (LP) f16 halves (slot 2w | 2w + 1 in word w, rec_words words) —
 // |c_t| <= t + 1 (c_t = f c_{t-1} + i g from zero), so no scaling: the backward's c_{t-1} and its rebuilt c_t carry
 // 2^-12 relative, as the f16 mode's h operands do.
+// In two steps where a wave-uniform branch decides the store (the forward's store rule, fcr_fwd.h): c_words forms the
+// f16 mode's words (pinned, so they are not sunk behind the branch), c_store_words stores them, or v itself in the
+// fp32 mode. The compiler contracts the cell update's last fma into the f16 conversion (one rounding instead of two)
+// only when both sit in one basic block, so WHERE the words are formed decides some halves' last bit.
+template <int HS, bool LP>
+__device__ __forceinline__ void c_words(const float (&v)[HS], float (&w)[HS]) {
+    if constexpr (LP) {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+        for (int d = 0; d < rec_words<HS, true>(); ++d) {
+            f16x2 p;
+            p[0] = (_Float16)v[2 * d];
+            p[1] = 2 * d + 1 < HS ? (_Float16)v[2 * d + 1 < HS ? 2 * d + 1 : 0] : (_Float16)0.0f;
+            w[d] = __builtin_bit_cast(float, p);
+            asm volatile("" : "+v"(w[d]));
+        }
+    }
+}
+template <int HS, bool LP>
+__device__ __forceinline__ void c_store_words(__amdgpu_buffer_rsrc_t r, uint32_t off, const float (&v)[HS],
+                                              const float (&w)[HS], int lane) {
+    if constexpr (LP) buf_store_rec<rec_words<HS, true>()>(r, off, w, lane);
+    else buf_store_quads<HS>(r, off, v, lane);
+}
 template <int HS, bool LP>
 __device__ __forceinline__ void c_store(__amdgpu_buffer_rsrc_t r, uint32_t off, const float (&v)[HS], int lane) {
     if constexpr (LP) {

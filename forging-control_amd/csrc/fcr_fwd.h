@@ -7,6 +7,11 @@
 // backward will run — so do c and the layer-0 window rows: the backward recomputes every gate from
 // (x_t, h_{t-1}, c_{t-1}) instead of reading stored activations (fcr_bwd.h), so the forward writes
 // 8 B per unit slot and cell instead of the 24 B of local derivatives.
+// Store rule (STORE = true): no backward reads a record before t_lo - 1 of its window (t_lo = max(0, 9 - window): the
+// cells a gradient can reach, fcr_bwd.h; the record contract at small_limit_of, fcr_rollout.hip), so in window j the h
+// and c records are stored for t >= t_lo(j) - 1 only, behind a wave-uniform branch; the rest of the slab stays holes
+// (36 of every 100 records per layer at N = 10). Stored whatever t: the window rows, and h1 in the fp32 mode (this
+// kernel's own layer-2 phase streams it back). The small-batch and pipelined forwards store every record.
 #pragma once
 #include "fcr_common.h"
 #include "fcr_f16.h"
@@ -217,6 +222,10 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
 
         const uint32_t oj = (uint32_t)((size_t)j * kLayers * kL * qcell * 16);   // window j's cells, [layer][t]
 #define SEQ_O(l, t) (oj + (uint32_t)(((l) * kL + (t)) * qcell * 16))
+        // The backward runs, in window j, only the cells t >= t_lo(j) = max(0, 9 - j) (fcr_bwd.h), which read the
+        // records of t >= t_lo - 1 and nothing before: only those are stored (wave-uniform: scalar branches). The
+        // others stay holes of the slab. h1 is this kernel's own layer-2 input in the fp32 mode: stored at every t.
+        const int t_rec = STORE ? (j < kL - 1 ? kL - 2 - j : 0) : 0;   // first t whose h, c records are kept
         const unsigned long long st_w1 = fstamp();
         st_head += st_w1 - st_w0;
         // ---- layers 0 and 1 together, time-major (Functions.py:374): layer 1's input h_t leaves layer 0's cell
@@ -231,27 +240,41 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
             const float *lw1 = LP ? lwl[1] : lw;
             float c1[HS], h1[HS];   // layer 1's c and the split record of its h
             float c2[LP ? HS : 1], h2[LP ? HS : 1];   // f16 mode: layer 2's
+            // f16 mode: which c words of the t >= 1 cells are formed beside the cell (c_words: one rounding) and which
+            // behind the store's branch (c_store: two). It reproduces, tier by tier, the halves this kernel stored
+            // before it had a store rule: the HS = 4, 8 loops ran with t = 9 peeled (every conversion beside its
+            // cell), the HS = 13 loop as written (the c conversions behind its t + 1 < kL branch).
+            constexpr bool CW_EARLY = LP && HS < 13;
+            auto c_put = [&](uint32_t off, const float (&cv)[HS], const float (&cwv)[HS]) {
+                if constexpr (CW_EARLY) c_store_words<HS, LP>(rc, off, cv, cwv, lane);
+                else c_store<HS, LP>(rc, off, cv, lane);
+            };
             {
+                const bool keep = t_rec <= 0;
+                float cw[HS];   // f16 mode: the c record's words, formed beside the cell that made c (c_words)
                 const float x0 = w0[0], x1 = w1[0];
                 rot_left(w0);
                 rot_left(w1);
                 fwd16_cell<HS, true, true, LP>(lw0, lane, x0, x1, hp, hp, c, hout, turn);
                 split_rec<HS, LP>(hout, hp);
                 if (STORE) {
-                    buf_store_rec<kRW>(rh, SEQ_O(0, 0), hp, lane);
+                    c_words<HS, LP>(c, cw);
+                    if (keep) buf_store_rec<kRW>(rh, SEQ_O(0, 0), hp, lane);
                     buf_st2(rx, lane * 8, (uint32_t)(j * kL * kWave * 8), f32x2{x0, x1});
-                    c_store<HS, LP>(rc, SEQ_O(0, 0), c, lane);
+                    if (keep) c_store_words<HS, LP>(rc, SEQ_O(0, 0), c, cw, lane);
                 }
                 fwd16_cell<HS, false, true, LP>(lw1, lane, 0.0f, 0.0f, hp, h1, c1, hout, turn);
                 split_rec<HS, LP>(hout, h1);
-                if (STORE || !LP) buf_store_rec<kRW>(rh, SEQ_O(1, 0), h1, lane);   // f16 mode: layer 2 is in this phase
-                if (STORE) c_store<HS, LP>(rc, SEQ_O(1, 0), c1, lane);
+                if (STORE) c_words<HS, LP>(c1, cw);
+                if (!LP || (STORE && keep)) buf_store_rec<kRW>(rh, SEQ_O(1, 0), h1, lane);   // f16 mode: layer 2 is in this phase
+                if (STORE && keep) c_store_words<HS, LP>(rc, SEQ_O(1, 0), c1, cw, lane);
                 if constexpr (LP) {   // every layer resident: layer 2 joins the phase (its h_t from registers as well)
                     fwd16_cell<HS, false, true, LP>(lwl[2], lane, 0.0f, 0.0f, h1, h2, c2, hout, turn);
                     split_rec<HS, LP>(hout, h2);
-                    if (STORE) {
+                    if (STORE) c_words<HS, LP>(c2, cw);
+                    if (STORE && keep) {
                         buf_store_rec<kRW>(rh, SEQ_O(2, 0), h2, lane);
-                        c_store<HS, LP>(rc, SEQ_O(2, 0), c2, lane);
+                        c_store_words<HS, LP>(rc, SEQ_O(2, 0), c2, cw, lane);
                     }
                 }
             }
@@ -261,22 +284,27 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
                 rot_left(w1);
                 fwd16_cell<HS, true, false, LP>(lw0, lane, x0, x1, hp, hp, c, hout, turn);
                 split_rec<HS, LP>(hout, hp);
+                const bool keep = t >= t_rec;
+                float cw[HS];
                 if (STORE) {
-                    buf_store_rec<kRW>(rh, SEQ_O(0, t), hp, lane);
+                    if (CW_EARLY) c_words<HS, LP>(c, cw);
+                    if (keep) buf_store_rec<kRW>(rh, SEQ_O(0, t), hp, lane);
                     buf_st2(rx, lane * 8, (uint32_t)((j * kL + t) * kWave * 8), f32x2{x0, x1});
-                    if (t + 1 < kL) c_store<HS, LP>(rc, SEQ_O(0, t), c, lane);   // c_9 is never a c_{t-1}
+                    if (keep && t + 1 < kL) c_put(SEQ_O(0, t), c, cw);   // c_9 is never a c_{t-1}
                 }
                 fwd16_cell<HS, false, false, LP>(lw1, lane, 0.0f, 0.0f, hp, h1, c1, hout, turn);
                 split_rec<HS, LP>(hout, h1);
-                if (STORE || !LP) buf_store_rec<kRW>(rh, SEQ_O(1, t), h1, lane);
-                if (STORE && t + 1 < kL) c_store<HS, LP>(rc, SEQ_O(1, t), c1, lane);
+                if (STORE && CW_EARLY) c_words<HS, LP>(c1, cw);
+                if (!LP || (STORE && keep)) buf_store_rec<kRW>(rh, SEQ_O(1, t), h1, lane);
+                if (STORE && keep && t + 1 < kL) c_put(SEQ_O(1, t), c1, cw);
                 if constexpr (LP) {
                     fwd16_cell<HS, false, false, LP>(lwl[2], lane, 0.0f, 0.0f, h1, h2, c2, hout, turn);
+                    if (STORE && CW_EARLY) c_words<HS, LP>(c2, cw);
                     if (t + 1 < kL) {   // h_9 of layer 2 only feeds the readout (fp32 hout)
                         split_rec<HS, LP>(hout, h2);
-                        if (STORE) {
+                        if (STORE && keep) {
                             buf_store_rec<kRW>(rh, SEQ_O(2, t), h2, lane);
-                            c_store<HS, LP>(rc, SEQ_O(2, t), c2, lane);
+                            c_put(SEQ_O(2, t), c2, cw);
                         }
                     }
                 }
@@ -295,8 +323,10 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
             buf_load_quads<HS>(xn, rh, SEQ_O(l - 1, 1), lane);
             fwd16_cell<HS, false, true, LP>(lwc, lane, 0.0f, 0.0f, xc, hp, c, hout, turn);
             split_rec<HS, LP>(hout, hp);
-            if (STORE) buf_store_rec<kRW>(rh, SEQ_O(l, 0), hp, lane);
-            if (STORE) c_store<HS, LP>(rc, SEQ_O(l, 0), c, lane);
+            if (STORE && t_rec <= 0) {
+                buf_store_rec<kRW>(rh, SEQ_O(l, 0), hp, lane);
+                c_store<HS, LP>(rc, SEQ_O(l, 0), c, lane);
+            }
 #pragma unroll
             for (int r = 0; r < HS; ++r) xc[r] = xn[r];
 #pragma unroll 3
@@ -305,9 +335,9 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
                 fwd16_cell<HS, false, false, LP>(lwc, lane, 0.0f, 0.0f, xc, hp, c, hout, turn);
                 if (t + 1 < kL) {   // h_9 of layer 2 only feeds the readout (fp32 hout)
                     split_rec<HS, LP>(hout, hp);
-                    if (STORE) buf_store_rec<kRW>(rh, SEQ_O(l, t), hp, lane);
+                    if (STORE && t >= t_rec) buf_store_rec<kRW>(rh, SEQ_O(l, t), hp, lane);
                 }
-                if (STORE && t + 1 < kL) c_store<HS, LP>(rc, SEQ_O(l, t), c, lane);
+                if (STORE && t >= t_rec && t + 1 < kL) c_store<HS, LP>(rc, SEQ_O(l, t), c, lane);
 #pragma unroll
                 for (int r = 0; r < HS; ++r) xc[r] = xn[r];
             }

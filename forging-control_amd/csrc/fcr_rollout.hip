@@ -104,8 +104,15 @@ int launch_bwd(const BwdArgs &ba, const Layout &L, bool lp, hipStream_t s) {
 // Small-batch kernels (fcr_small.h): one workgroup of ceil(HS/4) waves per 16-trajectory group.
 // Used for the fp32-accurate mode at HS = 8, 13 when B <= the call's small-batch limit (fcr_options; the
 // process-wide default g_small_max_batch when it inherits): below one wave per SIMD the fused kernels run at one
-// wave's sequential latency. A change between a forward and its backward is harmless: both families keep one
-// workspace layout, and a mixed pair is valid (tested).
+// wave's sequential latency. A change between a forward and its backward is harmless: every family keeps one
+// workspace layout and one record contract (tests/test_gpu_record_contract.py):
+//   - a forward with with_backward = 1 guarantees, in window j with t_lo = max(0, 9 - j), the window rows xw of every
+//     t, the h records of layers 0 and 2 and the c records of every layer at t >= t_lo - 1 (never c_9, never layer
+//     2's h_9), and h1 at t >= t_lo - 1 (the fused fp32 forward writes h1 at every t for its own layer-2 phase; the
+//     small-batch and pipelined forwards write every record). What lies before stays a hole of the slab;
+//   - every backward family reads only those: the fused backward runs only the cells t >= t_lo (fcr_bwd.h), which
+//     read x_t, h_{t-1}, c_{t-1} and their own h_t; the small-batch and pipelined backwards run every cell and clamp
+//     the records of the unreached ones to the written set (SbCtx::next_of, fcr_small.h).
 int small_limit_of(const fcr_options *o) {
     return (o && o->small_batch_limit >= 0) ? o->small_batch_limit : g_small_max_batch.load(std::memory_order_relaxed);
 }

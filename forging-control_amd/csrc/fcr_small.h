@@ -697,10 +697,17 @@ struct SbCtx {
             if (PIPE || l == 0) { nl = PIPE ? l : 2; nj = j - (PIPE ? S : 1); }
         }
         if (nj < 0) { nj = 0; nl = PIPE ? l : 2; nt = 9; }   // past the last cell: a valid one (harmless)
-        n.x = nl == 0 ? (uint32_t)((nj * kL + nt) * kWave * 8) : hoff(nj, nl > 0 ? nl - 1 : 0, nt);
-        n.h = hoff(nj, nl, nt > 0 ? nt - 1 : 0);
+        // Forward records: a with_backward forward guarantees, in window nj, the h and c records of t >= t_lo - 1 only
+        // (t_lo = max(0, 9 - nj): fcr_fwd.h's store rule, the contract at small_limit_of). A reached cell (nt >= t_lo)
+        // reads exactly those, at the offsets it always had. This schedule also runs the unreached cells, whose
+        // outputs go nowhere: they recompute from the nearest written records instead of a hole of the slab.
+        const int t_lo = nj < kL - 1 ? kL - 1 - nj : 0;
+        const int xt = nt > t_lo ? nt : t_lo;
+        const int ht = nt - 1 > t_lo - 1 ? nt - 1 : t_lo - 1;
+        n.x = nl == 0 ? (uint32_t)((nj * kL + xt) * kWave * 8) : hoff(nj, nl > 0 ? nl - 1 : 0, xt);
+        n.h = hoff(nj, nl, ht > 0 ? ht : 0);
         n.c = n.h;
-        n.d = (uint32_t)((nl < 2 ? doff(nj, nl + 1, nt) : 0) * 16);
+        n.d = (uint32_t)((nl < 2 ? doff(nj, nl + 1, nt) : 0) * 16);   // the backward's own hand-off: every cell's
         return n;
     }
     // PIPE: a layer workgroup's progress counter after cell (j, t) (its windows N-1-s, N-1-s-S, ..., t = 9 .. 0)
