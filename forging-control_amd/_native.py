@@ -32,7 +32,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_get_small_batch_limit", "fcr_set_small_pipe_limit", "fcr_get_small_pipe_limit", "fcr_set_small_pipe_sets",
            "fcr_get_small_pipe_sets", "fcr_set_wide_keep_budget", "fcr_get_wide_keep_budget", "fcr_last_error",
            "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
-           "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch")
+           "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch", "fcr_many_workspace_size",
+           "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many")
 LOSS_L1, LOSS_MSE = 0, 1
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
@@ -182,6 +183,18 @@ def load() -> ctypes.CDLL:
         lib.fcr_fnn_forward.restype = i32
         lib.fcr_fnn_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         lib.fcr_fnn_backward.restype = i32
+        # M controllers side by side (a pure addition to ABI 8)
+        lib.fcr_many_workspace_size.argtypes = [ctypes.POINTER(FcrDims), po, i32, i32, ctypes.POINTER(sz)]
+        lib.fcr_many_workspace_size.restype = i32
+        lib.fcr_forward_many.argtypes = [ctypes.POINTER(FcrDims), po, i32, ctypes.POINTER(FcrWeights),
+                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+        lib.fcr_forward_many.restype = i32
+        lib.fcr_backward_many.argtypes = [ctypes.POINTER(FcrDims), po, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.fcr_backward_many.restype = i32
+        lib.fcr_fnn_forward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.fcr_fnn_forward_many.restype = i32
+        lib.fcr_fnn_backward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.fcr_fnn_backward_many.restype = i32
         lib.fcr_set_small_batch_limit.argtypes = [i32]
         lib.fcr_set_small_batch_limit.restype = i32
         lib.fcr_get_small_batch_limit.argtypes = []
@@ -270,6 +283,15 @@ def workspace_bytes(dims: FcrDims, with_backward: bool, opts: FcrOptions | None 
     out = ctypes.c_size_t(0)
     check(load().fcr_workspace_size(ctypes.byref(dims), ctypes.byref(opts) if opts is not None else None,
                                     int(bool(with_backward)), ctypes.byref(out)), "fcr_workspace_size")
+    return int(out.value)
+
+
+def many_workspace_bytes(dims: FcrDims, n_models: int, with_backward: bool, opts: FcrOptions | None = None) -> int:
+    """fcr_many_workspace_size: scratch of fcr_forward_many (+ fcr_backward_many) for n_models models of shape dims."""
+    out = ctypes.c_size_t(0)
+    check(load().fcr_many_workspace_size(ctypes.byref(dims), ctypes.byref(opts) if opts is not None else None,
+                                         int(n_models), int(bool(with_backward)), ctypes.byref(out)),
+          "fcr_many_workspace_size")
     return int(out.value)
 
 

@@ -261,6 +261,66 @@ int fcr_backward(const fcr_dims *d, fcr_options *opts, const float *X, const flo
                             (hipStream_t)stream);
 }
 
+// The checks of the many-model entries, before any launch: the single call's dims, then what the MANY kernels cover
+static int many_check(const char *what, const fcr_dims *d, const fcr_options *o, int32_t n_models) {
+    if (const int rc = check_dims(d)) return rc;
+    if (n_models < 0) return fail(FCR_EINVAL, "%s: n_models=%d must be >= 0", what, n_models);
+    if (n_models > 65535) return fail(FCR_EUNSUPPORTED, "%s: n_models=%d: at most 65535 (a grid dimension)", what, n_models);
+    if (d->precision != FCR_PRECISION_FP32)
+        return fail(FCR_EUNSUPPORTED, "%s: precision=%d: the many-model kernels run FCR_PRECISION_FP32 (0) only", what,
+                    d->precision);
+    if (!many_supported(d))
+        return fail(FCR_EUNSUPPORTED, "%s: H=%d: the many-model kernels are built for the slot tiers 8 and 13 (H 17..52)",
+                    what, d->H);
+    const int limit = (o && o->small_batch_limit >= 0) ? o->small_batch_limit : g_small_max_batch.load();
+    if (d->B > limit)
+        return fail(FCR_EUNSUPPORTED, "%s: B=%d is above the small-batch limit %d (the many-model kernels are the "
+                    "small-batch family's)", what, d->B, limit);
+    if ((long long)n_models * d->B * d->N > (1LL << 31)) return fail(FCR_EINVAL, "%s: n_models*B*N too large", what);
+    return FCR_OK;
+}
+
+int fcr_many_workspace_size(const fcr_dims *dims, const fcr_options *opts, int32_t n_models, int with_backward,
+                            size_t *bytes) {
+    if (const int rc = many_check("fcr_many_workspace_size", dims, opts, n_models)) return rc;
+    if (!bytes) return fail(FCR_EINVAL, "bytes is NULL");
+    *bytes = many_workspace(dims, n_models, with_backward);
+    return FCR_OK;
+}
+
+int fcr_forward_many(const fcr_dims *d, fcr_options *opts, int32_t n_models, const fcr_weights *w, const float *X,
+                     const float *u0, const float *states, const float *noise, float *loss, float *cost, float *command,
+                     float *error, float *prediction, float *xhat, int with_backward, void *ws, size_t ws_bytes,
+                     void *stream) {
+    int rc = many_check("fcr_forward_many", d, opts, n_models);
+    if (rc) return rc;
+    if (n_models == 0) return FCR_OK;
+    if (!w || !X || !u0 || !states || !loss || !cost || !command || !error || !prediction || !ws)
+        return fail(FCR_EINVAL, "fcr_forward_many: a required pointer is NULL");
+    for (int l = 0; l < kLayers; ++l)
+        if (!w->w_ih[l] || !w->w_hh[l]) return fail(FCR_EINVAL, "fcr_forward_many: LSTM weight of layer %d is NULL", l);
+    if (!w->fc_w || !w->fc_b || !w->ctrl_w_inp || !w->ctrl_b_inp || !w->ctrl_w_out)
+        return fail(FCR_EINVAL, "fcr_forward_many: a weight pointer is NULL");
+    if ((rc = check_ws("fcr_forward_many", ws, ws_bytes, many_workspace(d, n_models, with_backward)))) return rc;
+    note_kernels(opts, FCR_KERNELS_SMALL);
+    return many_forward(d, n_models, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
+                        (char *)ws, (hipStream_t)stream);
+}
+
+int fcr_backward_many(const fcr_dims *d, fcr_options *opts, int32_t n_models, const float *X, const float *states,
+                      const float *prediction, const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp,
+                      float *g_w_out, void *ws, size_t ws_bytes, void *stream) {
+    int rc = many_check("fcr_backward_many", d, opts, n_models);
+    if (rc) return rc;
+    if (n_models == 0) return FCR_OK;
+    if (!X || !states || !prediction || !dloss || !g_u0 || !g_w_inp || !g_b_inp || !g_w_out || !ws)
+        return fail(FCR_EINVAL, "fcr_backward_many: a required pointer is NULL");
+    if ((rc = check_ws("fcr_backward_many", ws, ws_bytes, many_workspace(d, n_models, 1)))) return rc;
+    note_kernels(opts, FCR_KERNELS_SMALL);
+    return many_backward(d, n_models, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws,
+                         (hipStream_t)stream);
+}
+
 int fcr_lstm_workspace_size(const fcr_dims *dims, int with_backward, size_t *bytes) {
     int rc = check_lstm_dims(dims);
     if (rc) return rc;
@@ -366,6 +426,48 @@ int fcr_fnn_backward(int32_t B, int32_t in_dim, int32_t hidden, const float *X, 
         if (one) return FCR_OK;
     }
     return launch_grad_reduce((const float *)ws, blocks, hidden, g_w_inp, g_b_inp, g_w_out, s);
+}
+
+static int fnn_many_check(const char *what, int32_t n_models, int32_t B, int32_t in_dim, int32_t hidden) {
+    if (n_models < 0) return fail(FCR_EINVAL, "%s: n_models=%d must be >= 0", what, n_models);
+    if (n_models > 65535) return fail(FCR_EUNSUPPORTED, "%s: n_models=%d: at most 65535 (a grid dimension)", what, n_models);
+    return fnn_check(what, B, in_dim, hidden);
+}
+
+int fcr_fnn_forward_many(int32_t n_models, int32_t B, int32_t in_dim, int32_t hidden, const float *X, const float *w_inp,
+                         const float *b_inp, const float *w_out, float *u, void *stream) {
+    int rc = fnn_many_check("fcr_fnn_forward_many", n_models, B, in_dim, hidden);
+    if (rc) return rc;
+    if (B == 0 || n_models == 0) return FCR_OK;
+    if (!X || !w_inp || !b_inp || !w_out || !u) return fail(FCR_EINVAL, "fcr_fnn_forward_many: a required pointer is NULL");
+    hipLaunchKernelGGL(fnn::fnn_fwd_many_kernel, dim3((B + fnn::kFnnBlock - 1) / fnn::kFnnBlock, n_models),
+                       dim3(fnn::kFnnBlock), 0, (hipStream_t)stream, B, hidden, X, w_inp, b_inp, w_out, u);
+    return launch_check("fnn_fwd_many_kernel");
+}
+
+int fcr_fnn_backward_many(int32_t n_models, int32_t B, int32_t in_dim, int32_t hidden, const float *X, const float *w_inp,
+                          const float *b_inp, const float *w_out, const float *g_u, float *g_x, float *g_w_inp,
+                          float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes, void *stream) {
+    int rc = fnn_many_check("fcr_fnn_backward_many", n_models, B, in_dim, hidden);
+    if (rc) return rc;
+    if (n_models == 0) return FCR_OK;
+    if (!w_inp || !b_inp || !w_out || !g_w_inp || !g_b_inp || !g_w_out || (B && (!X || !g_u || !ws)))
+        return fail(FCR_EINVAL, "fcr_fnn_backward_many: a required pointer is NULL");
+    size_t need = 0;
+    if ((rc = fcr_fnn_workspace_size(B, hidden, &need))) return rc;
+    need *= (size_t)n_models;   // fcr_fnn_workspace_size(B, hidden) per model
+    if (ws_bytes < need) return fail(FCR_EWORKSPACE, "fcr_fnn_backward_many: ws has %zu bytes, needs %zu", ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int blocks = (int)((B + fnn::kFnnItems - 1) / fnn::kFnnItems);
+    if (blocks) {
+        const bool one = blocks == 1;   // one block per model writes that model's gradients itself (grad_out5)
+        hipLaunchKernelGGL(fnn::fnn_bwd_many_kernel, dim3(blocks, n_models), dim3(fnn::kFnnBlock), 0, s, B, hidden, X, w_inp,
+                           b_inp, w_out, g_u, g_x, (float *)ws, blocks, one ? g_w_inp : nullptr, one ? g_b_inp : nullptr,
+                           one ? g_w_out : nullptr);
+        if ((rc = launch_check("fnn_bwd_many_kernel"))) return rc;
+        if (one) return FCR_OK;
+    }
+    return launch_grad_reduce_many((const float *)ws, blocks, hidden, n_models, g_w_inp, g_b_inp, g_w_out, s);
 }
 
 }  // extern "C"

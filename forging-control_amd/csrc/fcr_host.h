@@ -80,6 +80,9 @@ int launch_ctrl_grads(const fcr_dims *d, const float *X, const float *xhat, cons
                       int ctrl_blocks, float *g_w_inp, float *g_b_inp, float *g_w_out, hipStream_t s);
 int launch_grad_reduce(const float *part, int blocks, int hidden, float *g_w_inp, float *g_b_inp, float *g_w_out,
                        hipStream_t s);
+// M stacked controllers (blockIdx.y = model): model m's `blocks` partials -> row m of the stacked gradients
+int launch_grad_reduce_many(const float *part, int blocks, int hidden, int n_models, float *g_w_inp, float *g_b_inp,
+                            float *g_w_out, hipStream_t s);
 int pipe_max_sets();   // the most window sets the pipelined forward runs (fcr_pipe.h)
 size_t rollout_workspace(const fcr_dims *d, int with_backward);
 int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, const float *X, const float *u0,
@@ -88,6 +91,15 @@ int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, 
 int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const float *states, const float *prediction,
                      const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                      hipStream_t s);
+// M controllers side by side through the one-workgroup small-batch kernels (fcr_small.h, MANY); d->B = one model's batch
+bool many_supported(const fcr_dims *d);   // slot tier 8 or 13
+size_t many_workspace(const fcr_dims *d, int n_models, int with_backward);
+int many_forward(const fcr_dims *d, int n_models, const fcr_weights *w, const float *X, const float *u0,
+                 const float *states, const float *noise, float *loss, float *cost, float *command, float *error,
+                 float *prediction, float *xhat, int with_backward, char *base, hipStream_t s);
+int many_backward(const fcr_dims *d, int n_models, const float *X, const float *states, const float *prediction,
+                  const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
+                  hipStream_t s);
 
 // ---- fcr_wide.hip ----
 size_t wide_workspace(const fcr_dims *d, int with_backward, int keep);

@@ -357,6 +357,13 @@ int launch_loss_reduce(const float *part, int n, int B, float *loss, hipStream_t
     return launch_check("loss_reduce_kernel");
 }
 
+int launch_grad_reduce_many(const float *part, int blocks, int hidden, int n_models, float *g_w_inp, float *g_b_inp,
+                            float *g_w_out, hipStream_t s) {
+    hipLaunchKernelGGL(grad_reduce_many_kernel, dim3(hidden * 5, n_models), dim3(256), 0, s, part, blocks, hidden, g_w_inp,
+                       g_b_inp, g_w_out);
+    return launch_check("grad_reduce_many_kernel");
+}
+
 int pipe_max_sets() { return Pipe<13>::MAX_SETS; }
 
 size_t rollout_workspace(const fcr_dims *d, int with_backward) { return make_layout(d, with_backward).total; }
@@ -466,6 +473,161 @@ int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const
     if (rc) return rc;
     return launch_ctrl_grads(d, X, ba.xhat, ba.dv, ba.p.fnp, (float *)(base + L.fnn_part), L.ctrl_blocks, g_w_inp, g_b_inp,
                              g_w_out, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// M controllers side by side (fcr_forward_many / fcr_backward_many): the one-workgroup small-batch kernels' MANY
+// instantiations (fcr_small.h) on a grid of M * gpm groups, gpm = ceil(B / 16). d->B is the batch of ONE model; the
+// inputs and outputs are stacked model-major. Shared: the LSTM fragments and images, the readout, the range guard (its
+// scale belongs to the shared W_ih0, so it is taken over the stacked batch; s_c = 0 for every input the reference's
+// scalers produce, and then nothing differs from M separate calls). Per model: the controller records, the loss, the
+// controller gradients, each in the single-model kernels' summation order, so a model's numbers do not depend on M.
+namespace {
+
+struct ManyLayout : PackedLayout {
+    int gpm, nw, ctrl_blocks;
+    size_t fnp_many, xhat, dv, loss_part, fnn_part, hseq, cseq, xw, dseq, dxrow, stamp, total;
+};
+ManyLayout make_many(const fcr_dims *d, int M, int with_backward) {
+    ManyLayout L{};
+    L.HS = slot_tier(d->H);
+    L.gpm = (d->B + kTile - 1) / kTile;
+    L.nw = M * L.gpm;
+    const size_t rows = (size_t)M * d->B;
+    Arena take;
+    take_packed(take, L, with_backward != 0);
+    L.fnp_many = take(sizeof(float) * (size_t)M * kMS * 4 * kFnpStride);
+    L.xhat = take(sizeof(float) * rows * d->N * kOut);
+    L.loss_part = take(sizeof(float) * L.nw);
+    L.dv = take(sizeof(float) * rows * d->N);
+    L.ctrl_blocks = (int)(((long long)d->B * d->N + kCtrlItems - 1) / kCtrlItems);
+    L.fnn_part = take(sizeof(float) * (size_t)M * L.ctrl_blocks * d->ctrl_hidden * 5);
+    const size_t qcells = (size_t)L.nw * d->N * kLayers * kL * L.HS * 16;   // Geo<HS>::QC per cell
+    L.hseq = take(sizeof(f32x4) * qcells);
+    if (with_backward) {
+        L.cseq = take(sizeof(f32x4) * qcells);
+        L.xw = take(sizeof(f32x2) * (size_t)L.nw * d->N * kL * kWave);
+        L.dseq = take(sizeof(f32x4) * (size_t)L.nw * d->N * 2 * kL * L.HS * 16);
+        L.dxrow = take(sizeof(f32x2) * (size_t)4 * L.nw * d->N * kL * kWave);   // one copy per wave of a group
+    }
+#if FCR_STAMP
+    L.stamp = take(sizeof(unsigned long long) * L.nw * 4 * 16);
+#endif
+    L.total = take.off;
+    return L;
+}
+
+template <int HS, bool STORE>
+int launch_sfwd_many_t(const FwdArgs &fa, const ManyLayout &L, hipStream_t s) {
+    constexpr int lds = Small<HS>::LDS_FWD;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (const int rc = lds_attr((const void *)fcr_sfwd_kernel<HS, STORE, true>, lds, attr_done, "sfwd_many")) return rc;
+    hipLaunchKernelGGL((fcr_sfwd_kernel<HS, STORE, true>), dim3(L.nw), dim3(Small<HS>::NQ * kWave), lds, s, fa);
+    return launch_check("fcr_sfwd_kernel<MANY>");
+}
+template <int HS>
+int launch_sbwd_many_t(const BwdArgs &ba, const ManyLayout &L, hipStream_t s) {
+    constexpr int lds = Small<HS>::LDS_BWD;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (const int rc = lds_attr((const void *)fcr_sbwd_kernel<HS, true>, lds, attr_done, "sbwd_many")) return rc;
+    hipLaunchKernelGGL((fcr_sbwd_kernel<HS, true>), dim3(L.nw), dim3(Small<HS>::NQ * kWave), lds, s, ba);
+    return launch_check("fcr_sbwd_kernel<MANY>");
+}
+
+}  // namespace
+
+bool many_supported(const fcr_dims *d) {
+    const int HS = slot_tier(d->H);
+    return !is_wide(d) && (HS == 8 || HS == 13);
+}
+
+size_t many_workspace(const fcr_dims *d, int n_models, int with_backward) {
+    return make_many(d, n_models, with_backward).total;
+}
+
+int many_forward(const fcr_dims *d, int M, const fcr_weights *w, const float *X, const float *u0, const float *states,
+                 const float *noise, float *loss, float *cost, float *command, float *error, float *prediction,
+                 float *xhat, int with_backward, char *base, hipStream_t s) {
+    int rc;
+    const ManyLayout L = make_many(d, M, with_backward);
+    fcr_dims all = *d;   // the range guard over the stacked batch
+    all.B = M * d->B;
+    if ((rc = launch_range(&all, states, u0, noise, w->fc_w, w->fc_b, (float *)(base + L.rng), (float *)(base + L.wsc), s)))
+        return rc;
+    // the shared packs once (no controller: CH = 0), then the M controllers' records
+    if ((rc = launch_pack_all(w, d->H, 0, L, with_backward != 0, base, nullptr, 0, s))) return rc;
+    constexpr int nf = kMS * 4 * kFnpStride;
+    hipLaunchKernelGGL(pack_fnp_many_kernel, dim3((nf + 255) / 256, M), dim3(256), 0, s, w->ctrl_w_inp, w->ctrl_b_inp,
+                       w->ctrl_w_out, d->ctrl_hidden, (float *)(base + L.fnp_many));
+    if ((rc = launch_check("pack_fnp_many_kernel"))) return rc;
+
+    FwdArgs fa{};
+    fa.B = d->B;
+    fa.N = d->N;
+    fa.alpha = d->alpha;
+    fa.X = X;
+    fa.u0 = u0;
+    fa.states = states;
+    fa.noise = noise;
+    fa.cost = cost;
+    fa.command = command;
+    fa.error = error;
+    fa.prediction = prediction;
+    fa.xhat_user = xhat;
+    fa.xhat_ws = (float *)(base + L.xhat);
+    fa.loss_part = (float *)(base + L.loss_part);
+    fa.hseq = (f32x4 *)(base + L.hseq);
+    fa.cseq = with_backward ? (f32x4 *)(base + L.cseq) : nullptr;
+    fa.xw = with_backward ? (f32x2 *)(base + L.xw) : nullptr;
+    fa.p = packed_ptrs(L, base);
+    fa.p.fnp = (const float *)(base + L.fnp_many);
+#if FCR_STAMP
+    fa.stamp = (unsigned long long *)(base + L.stamp) + (size_t)L.nw * 4 * 8;
+#endif
+    if (L.HS == 8) rc = with_backward ? launch_sfwd_many_t<8, true>(fa, L, s) : launch_sfwd_many_t<8, false>(fa, L, s);
+    else rc = with_backward ? launch_sfwd_many_t<13, true>(fa, L, s) : launch_sfwd_many_t<13, false>(fa, L, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_reduce_many_kernel, dim3(M), dim3(256), 0, s, (const float *)fa.loss_part, L.gpm, d->B, loss);
+    return launch_check("loss_reduce_many_kernel");
+}
+
+int many_backward(const fcr_dims *d, int M, const float *X, const float *states, const float *prediction,
+                  const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
+                  hipStream_t s) {
+    int rc;
+    const ManyLayout L = make_many(d, M, 1);
+    BwdArgs ba{};
+    ba.B = d->B;
+    ba.N = d->N;
+    ba.hidden = d->ctrl_hidden;
+    ba.alpha = d->alpha;
+    ba.X = X;
+    ba.states = states;
+    ba.prediction = prediction;
+    ba.xhat = (const float *)(base + L.xhat);
+    ba.dloss = dloss;
+    ba.hseq = (const f32x4 *)(base + L.hseq);
+    ba.cseq = (const f32x4 *)(base + L.cseq);
+    ba.xw = (const f32x2 *)(base + L.xw);
+    ba.dseq = (f32x4 *)(base + L.dseq);
+    ba.dxrow = (f32x2 *)(base + L.dxrow);
+    ba.g_u0 = g_u0;
+    ba.dv = (float *)(base + L.dv);
+#if FCR_STAMP
+    ba.stamp = (unsigned long long *)(base + L.stamp);
+#endif
+    ba.p = packed_ptrs(L, base);
+    ba.p.fnp = (const float *)(base + L.fnp_many);
+    rc = L.HS == 8 ? launch_sbwd_many_t<8>(ba, L, s) : launch_sbwd_many_t<13>(ba, L, s);
+    if (rc) return rc;
+    float *part = (float *)(base + L.fnn_part);
+    const bool one = L.ctrl_blocks == 1;   // one block per model writes that model's gradients itself (grad_out5)
+    hipLaunchKernelGGL(ctrl_grad_many_kernel, dim3(L.ctrl_blocks, M), dim3(kCtrlBlock), 0, s, X, ba.xhat, (const float *)ba.dv,
+                       ba.p.fnp, d->B, d->N, d->ctrl_hidden, part, L.ctrl_blocks, one ? g_w_inp : nullptr,
+                       one ? g_b_inp : nullptr, one ? g_w_out : nullptr);
+    if ((rc = launch_check("ctrl_grad_many_kernel"))) return rc;
+    if (one) return FCR_OK;
+    return launch_grad_reduce_many(part, L.ctrl_blocks, d->ctrl_hidden, M, g_w_inp, g_b_inp, g_w_out, s);
 }
 
 namespace {

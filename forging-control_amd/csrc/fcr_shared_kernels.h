@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kRangeThreads) void range_partial_kernel(const floa
 __global__ void pack_misc_kernel(PackArgs a) { pack_misc_item(a, blockIdx.x * blockDim.x + threadIdx.x); }
 
 // loss = sum(loss_part[0..nw)) / B, fixed order (one block)
-__global__ void loss_reduce_kernel(const float *part, int nw, int B, float *loss) {
+__device__ __forceinline__ void loss_reduce_block(const float *part, int nw, int B, float *loss) {
     __shared__ float red[256];
     float s = 0.0f;
     for (int i = threadIdx.x; i < nw; i += blockDim.x) s += part[i];
@@ -76,15 +76,19 @@ __global__ void loss_reduce_kernel(const float *part, int nw, int B, float *loss
     }
     if (threadIdx.x == 0) loss[0] = red[0] / (float)B;
 }
+__global__ void loss_reduce_kernel(const float *part, int nw, int B, float *loss) { loss_reduce_block(part, nw, B, loss); }
+// M models (fcr_forward_many): block m sums model m's gpm partials in the same order -> loss[m]
+__global__ void loss_reduce_many_kernel(const float *part, int gpm, int B, float *loss) {
+    loss_reduce_block(part + (size_t)blockIdx.x * gpm, gpm, B, loss + blockIdx.x);
+}
 
 // Controller parameter gradients (the in-loss controller calls, Functions.py:1424-1430), from the dv
 // the backward kernel stored per (trajectory, step): z = W_inp·[x0, x3, ref] + b is recomputed from
 // the stored xhat with the same arithmetic as fnn_pre; dz = dv·w_out·1[z>0]. One block per chunk of
 // (trajectory, step) items; a wave's lanes are the hidden units; fixed-order sums everywhere.
-__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_kernel(const float *X, const float *xhat, const float *dv,
-                                                               const float *fnp, int B, int N, int hidden,
-                                                               float *part, float *gwi = nullptr,
-                                                               float *gbi = nullptr, float *gwo = nullptr) {
+__device__ __forceinline__ void ctrl_grad_block(const float *X, const float *xhat, const float *dv, const float *fnp,
+                                                int B, int N, int hidden, float *part, float *gwi, float *gbi,
+                                                float *gwo) {
     __shared__ float sx0[kCtrlItems], sx3[kCtrlItems], sref[kCtrlItems], sdv[kCtrlItems];
     __shared__ float red[kCtrlBlock / kWave][64][5];
     const long long items = (long long)B * N;
@@ -129,10 +133,27 @@ __global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_kernel(const float *X, c
         }
     }
 }
+__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_kernel(const float *X, const float *xhat, const float *dv,
+                                                               const float *fnp, int B, int N, int hidden,
+                                                               float *part, float *gwi = nullptr,
+                                                               float *gbi = nullptr, float *gwo = nullptr) {
+    ctrl_grad_block(X, xhat, dv, fnp, B, N, hidden, part, gwi, gbi, gwo);
+}
+// M models (fcr_backward_many): blockIdx.y = m runs ctrl_grad_kernel's blocks over model m's B * N items of the stacked
+// (M, B, ...) arrays with that model's records; `blocks` = the blocks per model (the stride of the partials)
+__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_many_kernel(const float *X, const float *xhat, const float *dv,
+                                                                    const float *fnp, int B, int N, int hidden,
+                                                                    float *part, int blocks, float *gwi, float *gbi,
+                                                                    float *gwo) {
+    const size_t m = blockIdx.y, rows = m * B;
+    ctrl_grad_block(X + rows * kCtrlIn, xhat + rows * N * kOut, dv + rows * N, fnp + m * (kMS * 4 * kFnpStride), B, N, hidden,
+                    part + m * blocks * hidden * 5, gwi ? gwi + m * hidden * kCtrlIn : nullptr,
+                    gwi ? gbi + m * hidden : nullptr, gwi ? gwo + m * hidden : nullptr);
+}
 
 // grads: one block per (unit k, param p); sum over waves in fixed order
-__global__ void grad_reduce_kernel(const float *part, int nw, int hidden, float *gwi, float *gbi,
-                                   float *gwo) {
+__device__ __forceinline__ void grad_reduce_block(const float *part, int nw, int hidden, float *gwi, float *gbi,
+                                                  float *gwo) {
     __shared__ float red[256];
     const int kp = blockIdx.x, k = kp / 5, p = kp % 5;
     float s = 0.0f;
@@ -149,6 +170,32 @@ __global__ void grad_reduce_kernel(const float *part, int nw, int hidden, float 
         else if (p == 3) gbi[k] = v;
         else gwo[k] = v;
     }
+}
+__global__ void grad_reduce_kernel(const float *part, int nw, int hidden, float *gwi, float *gbi,
+                                   float *gwo) {
+    grad_reduce_block(part, nw, hidden, gwi, gbi, gwo);
+}
+// M models: blockIdx.y = m sums model m's nw partials -> row m of the stacked gradients
+__global__ void grad_reduce_many_kernel(const float *part, int nw, int hidden, float *gwi, float *gbi, float *gwo) {
+    const size_t m = blockIdx.y;
+    grad_reduce_block(part + m * nw * hidden * 5, nw, hidden, gwi + m * hidden * kCtrlIn, gbi + m * hidden,
+                      gwo + m * hidden);
+}
+
+// the controller records of M stacked controllers (pack_misc_item's fnp part per model): blockIdx.y = m
+__global__ void pack_fnp_many_kernel(const float *cwi, const float *cbi, const float *cwo, int CH, float *fnp) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    constexpr int nf = kMS * 4 * kFnpStride;
+    if (idx >= nf) return;
+    const size_t m = blockIdx.y;
+    const int p = idx % kFnpStride, q = (idx / kFnpStride) & 3, k = 4 * (idx / (kFnpStride * 4)) + q;
+    float v = 0.0f;
+    if (k < CH) {
+        if (p < 3) v = cwi[(m * CH + k) * kCtrlIn + p];
+        else if (p == 3) v = cbi[m * CH + k];
+        else if (p == 4) v = cwo[m * CH + k];
+    }
+    fnp[m * nf + idx] = v;
 }
 
 // the LSTM weight packs as launches of their own (pack_all_kernel, fcr_rollout.hip, runs the same items as jobs)

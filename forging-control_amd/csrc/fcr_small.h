@@ -129,6 +129,24 @@ struct Small {
     static_assert(Geo16<HS>::LDS_FWD % 16 == 0 && BwdLds<HS, false>::BYTES % 16 == 0, "16-B aligned buffers");
 };
 
+// Which model a group belongs to (the MANY instantiations, fcr_forward_many): model m owns groups m * gpm ..
+// (m + 1) * gpm - 1, gpm = ceil(B / 16), and rows m * B .. (m + 1) * B - 1 of the stacked inputs. Without MANY
+// every member is a compile-time 0 / the identity, so the single-model kernels are what they were.
+template <bool MANY>
+struct ManyIdx {
+    int m, g0;   // model, its first group
+    __device__ ManyIdx(int grp, int B) : m(0), g0(0) {
+        if constexpr (MANY) {
+            const int gpm = (B + kTile - 1) / kTile;
+            m = grp / gpm;
+            g0 = m * gpm;
+        }
+    }
+    __device__ int model() const { return MANY ? m : 0; }
+    __device__ int lgrp(int grp) const { return MANY ? grp - g0 : grp; }   // the group's index within its model
+    __device__ int row0(int B) const { return MANY ? m * B : 0; }          // the model's first row
+};
+
 template <int V>
 struct IC {
     static constexpr int v = V;
@@ -232,7 +250,11 @@ __device__ __forceinline__ void xchg_get(const f32x4 *xb, float (&h)[HS], int la
 // ---------------------------------------------------------------------------------------------------
 // forward: the fused forward kernel's program (fcr_fwd.h) with the cell's tiles split over the waves
 // ---------------------------------------------------------------------------------------------------
-template <int HS, bool STORE>
+// MANY (fcr_forward_many): M controllers side by side. The grid is M * gpm workgroups, gpm = ceil(B / 16) groups per
+// model with a.B the batch of ONE model; group grp belongs to model m = grp / gpm, stages that model's controller
+// records (a.p.fnp + m * FNP) and runs rows m * B + local row of the stacked (M, B, ...) inputs and outputs; an invalid
+// lane reads its own model's last row. Slabs, xw and loss_part stay indexed by grp. Nothing else differs.
+template <int HS, bool STORE, bool MANY = false>
 __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sfwd_kernel(FwdArgs a) {
     using G = Geo16<HS>;
     constexpr int NQ = Small<HS>::NQ;
@@ -244,18 +266,19 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sfwd_kernel(FwdA
     float *lfcb = lfcp + G::FCP;
     f32x4 *xbuf = reinterpret_cast<f32x4 *>(lw + G::LDS_FWD / 4);
     constexpr int RECB = Geo<HS>::QC * 16;   // one split record (bytes); two of them double-buffer the exchange
+    const ManyIdx<MANY> mi(blockIdx.x, a.B);
     lds_copy(lw0, a.p.fa[0], G::FA0);
-    lds_copy(lfnp, a.p.fnp, G::FNP);
+    lds_copy(lfnp, a.p.fnp + mi.model() * G::FNP, G::FNP);
     lds_copy(lfcp, a.p.fcp, G::FCP);
     lds_copy(lfcb, a.p.fcb, 4);
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, sl = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = blockIdx.x;   // the fused kernels' wave index: same slab regions
-    const int b = grp * kTile + sl;
-    const bool valid = b < a.B;
+    const int b = mi.row0(a.B) + mi.lgrp(grp) * kTile + sl;
+    const bool valid = mi.lgrp(grp) * kTile + sl < a.B;
     const bool lead = w == 0;     // writes the per-trajectory outputs
-    const int bc = valid ? b : a.B - 1;
+    const int bc = valid ? b : mi.row0(a.B) + a.B - 1;
     const int N = a.N;
     const float alpha = a.alpha;
 
@@ -904,7 +927,8 @@ __device__ __forceinline__ void sb_phase(const SbCtx<HS, PIPE> &x, int j, const 
                                                                                               dc);
 }
 
-template <int HS>
+// MANY (fcr_backward_many): the forward's indexing (ManyIdx); a.dloss holds one float per model
+template <int HS, bool MANY = false>
 __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sbwd_kernel(BwdArgs a) {
     using LD = BwdLds<HS, false>;
     using I1 = Img<HS, false>;
@@ -913,20 +937,21 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sbwd_kernel(BwdA
     extern __shared__ __attribute__((aligned(16))) float lw[];
     float *lfnp = lw + LD::REGION / 4;
     float *lfcp = lfnp + LD::FNP;
-    lds_copy(lfnp, a.p.fnp, LD::FNP);
+    const ManyIdx<MANY> mi(blockIdx.x, a.B);
+    lds_copy(lfnp, a.p.fnp + mi.model() * LD::FNP, LD::FNP);
     lds_copy(lfcp, a.p.fcp, LD::FCP);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int q = lane >> 4, sl = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = blockIdx.x;
-    const int b = grp * kTile + sl;
-    const bool valid = b < a.B;
+    const int b = mi.row0(a.B) + mi.lgrp(grp) * kTile + sl;
+    const bool valid = mi.lgrp(grp) * kTile + sl < a.B;
     const bool lead = w == 0;
-    const int bc = valid ? b : a.B - 1;
+    const int bc = valid ? b : mi.row0(a.B) + a.B - 1;
     const int N = a.N;
     const float alpha = a.alpha;
-    const float wgt = valid ? a.dloss[0] / ((float)a.B * (float)N) : 0.0f;   // Functions.py:1458, 1463
+    const float wgt = valid ? a.dloss[mi.model()] / ((float)a.B * (float)N) : 0.0f;   // Functions.py:1458, 1463
     const float ref = a.X[(size_t)bc * kCtrlIn + 2];
     const float s84 = a.states[(size_t)bc * kL * kIn + (kL - 2) * kIn + 4];
     const float *pred = a.prediction + (size_t)bc * N;

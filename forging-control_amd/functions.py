@@ -123,17 +123,19 @@ class MPCLoss(nn.Module):
     the process-wide default): ``small_batch_limit`` — B at or below it runs the small-batch kernels (0 = never);
     ``wide_keep_budget`` — H > 52, bytes of kept windows the workspace may add ("auto": the library's policy).
     ``self.last_call`` (a :class:`~.rollout.CallInfo`) reports the kernel families the last call's passes launched
-    and its workspace.
+    and its workspace. ``many_min_models``: the least M at which :meth:`forward_many` runs the many-model kernels
+    (None: :data:`.many.MANY_MIN_MODELS`, the measured crossover).
     """
 
     def __init__(self, prediction_horizon=10, alpha=0.1, precision="fp32", small_batch_limit=None,
-                 wide_keep_budget=None):
+                 wide_keep_budget=None, many_min_models=None):
         super().__init__()
         self.N = prediction_horizon
         self.alpha = alpha
         self.precision = precision     # "fp32" (reference-accurate) or "f16" (config 3, include/fcr.h)
         self.small_batch_limit = small_batch_limit
         self.wide_keep_budget = wide_keep_budget
+        self.many_min_models = many_min_models
         self.activation = nn.ReLU()
         self.last_trajectory = None
         self.last_call = None
@@ -160,6 +162,27 @@ class MPCLoss(nn.Module):
             self.N, self.alpha, noise, self.precision, self.last_call)
         self.last_trajectory = xhat
         return loss, {"loss": cost, "command": command, "error": error, "prediction": prediction}
+
+    def forward_many(self, simulator: nn.Module, bank: nn.Module, input_controller: torch.Tensor,
+                     output_controller: torch.Tensor, states: torch.Tensor, device: torch.device,
+                     enable_noise=False, noise: torch.Tensor | None = None):
+        """:meth:`forward` for the M controllers of a :class:`~.many.ControllerBank` against one shared simulator, on
+        inputs stacked model-major: ``X (M,B,3)``, ``u0 (M,B,1)``, ``states (M,B,10,5)``, ``noise (M,B,N,4)`` or None.
+        Returns ``(losses (M,), features)`` with ``loss`` / ``command`` / ``error`` as ``(M,B)`` and ``prediction`` as
+        ``(M, B*N)``; ``self.last_trajectory`` is ``(M,B,N,4)``. Model m's numbers are those of
+        ``forward(simulator, controller_m, X[m], u0[m], states[m], ...)``: ``losses[m]`` is the mean over its own B
+        trajectories and nothing sums over models, so ``losses.sum().backward()`` gives every model its own gradient
+        and ``(losses * w).sum().backward()`` scales model m's by ``w[m]``. With ``enable_noise`` and no ``noise`` the
+        draws are those of M successive single-model calls, model 0 first.
+
+        On a ROCm device with ``precision == "fp32"``, H in 17..52, ``B <=`` the small-batch limit and
+        ``M >= many_min_models`` each pass is ONE launch of the many-model kernels (a workgroup per 16-trajectory group
+        of one model); anything else — CPU tensors, H > 52, f16, a large B — loops over the models through
+        :meth:`forward`, with the same results. ``self.last_call`` (a :class:`~.many.ManyCallInfo`) says which route
+        ran (``route``: "many" or "loop", and ``why``)."""
+        from .many import forward_many
+        return forward_many(self, simulator, bank, input_controller, output_controller, states, device, enable_noise,
+                            noise)
 
     def _forward_host(self, simulator, controller, X, u0, states, device, enable_noise, noise):
         """The rollout where the reference runs it without a GPU (``device = cpu``, UL/Main.py:38): its op
@@ -263,6 +286,30 @@ class NeuralNetwork:
             n_batches += 1
         feats = {k: torch.cat(v, dim=0) if v else torch.empty(0, device=device) for k, v in feats.items()}
         return total / max(n_batches, 1), feats
+
+    @staticmethod
+    def captured_models_step(simulator, bank, loss_function, optimizer, device, enable_noise=False, warmup=2):
+        """The body of :meth:`train_models`' batch loop as a :class:`~.graphed.CapturedStep` (pass it as
+        ``train_models(..., step=...)``, reusable across epochs)."""
+        from .many import captured_models_step
+        return captured_models_step(simulator, bank, loss_function, optimizer, device, enable_noise, warmup)
+
+    @staticmethod
+    def train_models(batches, simulator, bank, loss_function, optimizer, device, enable_noise=False, step=None):
+        """One epoch of :meth:`train_model` for the M controllers of a :class:`~.many.ControllerBank` side by side:
+        ``batches`` yields stacked ``(X (M,B,3), y, states (M,B,10,5))`` (:func:`~.many.zip_loaders` makes them from M
+        loaders, each model keeping its own shuffling). Per batch: ``bank(X)``, ``loss_function.forward_many``,
+        ``losses.sum().backward()``, ``optimizer.step()``. Returns ``(per-model average losses, features)`` with the
+        features concatenated along the batch: ``(M, ΣB)``, prediction ``(M, ΣB·N)``.
+
+        One ``torch.optim.AdamW(bank.parameters())`` IS M independent AdamWs: its update is element-wise (moments,
+        bias correction, decoupled weight decay, one shared step count), the models' losses are independent, and the
+        sum's gradient of model m's rows is ``losses[m]``'s — so row m of the bank moves exactly as controller m would
+        under its own AdamW with the same hyper-parameters. (An optimizer with a cross-parameter term — gradient-norm
+        clipping over all parameters, LAMB's trust ratio — would couple the models.) ``step`` (from
+        :meth:`captured_models_step`) replays each batch's step from a HIP graph."""
+        from .many import train_models
+        return train_models(batches, simulator, bank, loss_function, optimizer, device, enable_noise, step)
 
     @staticmethod
     def _train_model_captured(data_loader, step, device):

@@ -163,6 +163,45 @@ int fcr_fnn_backward(int32_t B, int32_t in_dim, int32_t hidden, const float *X, 
                      float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * M controllers side by side (the reference ships ten seeds of the controller, all trained at B = 15): n_models
+ * controllers of one hidden width against ONE shared LSTM surrogate, one rollout launch per pass. A pure addition to
+ * ABI v8 (no existing call or struct changed): look the symbols up.
+ *   dims       the shape of ONE model's call (dims->B = its batch; every model has the same B)
+ *   w          ctrl_w_inp (M,hidden,3), ctrl_b_inp (M,hidden), ctrl_w_out (M,hidden) stacked; the LSTM's as in fcr_weights
+ *   X (M,B,3), u0 (M,B,1), states (M,B,L,5), noise (M,B,N,4) or NULL — stacked model-major
+ *   loss (M), cost/command/error (M,B), prediction (M,B*N), xhat (M,B,N,4) or NULL
+ *   dloss (M) DEVICE floats; g_u0 (M,B,1), g_w_inp (M,hidden,3), g_b_inp (M,hidden), g_w_out (M,hidden), OVERWRITTEN
+ * Model m's results are what fcr_forward / fcr_backward return for (controller m, X[m], u0[m], states[m], noise[m]):
+ * loss[m] is the mean over its own B trajectories, nothing sums over models, every sum keeps the single call's order
+ * (a model's numbers do not depend on M). One thing is shared: the f16 split's range guard scales a window column by
+ * the maximum over the STACKED batch, because the scale belongs to the shared W_ih0; for every input the reference's
+ * scalers produce that scale is 2^0 and nothing differs from M separate calls.
+ * Kernels: the small-batch family's one-workgroup geometry, a 16-trajectory group of one model per workgroup. Refused
+ * before any launch: n_models < 0 (FCR_EINVAL); precision other than FCR_PRECISION_FP32, an H outside the slot tiers
+ * 8 and 13 (17..52), B above the small-batch limit (opts, else the process default) — FCR_EUNSUPPORTED: run those as
+ * n_models single calls. n_models = 0 is a no-op. Scratch: fcr_many_workspace_size bytes, 256-byte aligned.
+ * fcr_fnn_forward_many / fcr_fnn_backward_many are fcr_fnn_forward / _backward for the stacked controllers on
+ * X (M,B,3) -> u (M,B,1); scratch of the backward: n_models * fcr_fnn_workspace_size(B, hidden) bytes.
+ */
+int fcr_many_workspace_size(const fcr_dims *dims, const fcr_options *opts, int32_t n_models, int with_backward,
+                            size_t *bytes);
+int fcr_forward_many(const fcr_dims *dims, fcr_options *opts, int32_t n_models, const fcr_weights *w,
+                     const float *X, const float *u0, const float *states, const float *noise,
+                     float *loss, float *cost, float *command, float *error,
+                     float *prediction, float *xhat,
+                     int with_backward, void *ws, size_t ws_bytes, void *stream);
+int fcr_backward_many(const fcr_dims *dims, fcr_options *opts, int32_t n_models,
+                      const float *X, const float *states, const float *prediction,
+                      const float *dloss,
+                      float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out,
+                      void *ws, size_t ws_bytes, void *stream);
+int fcr_fnn_forward_many(int32_t n_models, int32_t B, int32_t in_dim, int32_t hidden, const float *X,
+                         const float *w_inp, const float *b_inp, const float *w_out, float *u, void *stream);
+int fcr_fnn_backward_many(int32_t n_models, int32_t B, int32_t in_dim, int32_t hidden, const float *X,
+                          const float *w_inp, const float *b_inp, const float *w_out, const float *g_u, float *g_x,
+                          float *g_w_inp, float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Batched forging-press plant: the state update x_{t+1} = F(x_t, u_t) of
  * FeasibilityRecovery.Ruge_Kuta (Functions.py:1743-1781) over the dynamics of forging_model
  * (Functions.py:1615-1740; smooth = 1: template_model.py:19-149, pressures floored by smooth_relu),

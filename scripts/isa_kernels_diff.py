@@ -6,7 +6,8 @@ whatever order. Reports kernels missing from DIR_B, added in DIR_B, or textually
 (0: same kernels, same code). A kernel compiled into several files of one directory (a template instantiated in two
 translation units) must be the same in each.
 --renamed-ok: a kernel missing under one symbol and added under another with the same bare function name and identical
-code (one that moved into or out of a namespace) is listed as renamed, not as a difference."""
+code (one that moved into or out of a namespace, or whose template gained a defaulted argument) is listed as renamed, not
+as a difference; of several added symbols with that name, the one with the identical code is its twin."""
 import glob
 import os
 import re
@@ -72,8 +73,8 @@ def main(argv):
     differ = sorted(n for n in set(a) & set(b) if a[n] != b[n])
     renamed = []
     for n in list(missing):
-        twins = [m for m in added if bare(m) == bare(n)]
-        if len(twins) == 1 and a[n].replace(n, "@") == b[twins[0]].replace(twins[0], "@"):
+        twins = [m for m in added if bare(m) == bare(n) and a[n].replace(n, "@") == b[m].replace(m, "@")]
+        if len(twins) == 1:
             renamed.append((n, twins[0]))
             missing.remove(n)
             added.remove(twins[0])

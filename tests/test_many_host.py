@@ -1,0 +1,265 @@
+"""CPU: M controllers side by side (forging-control_amd/many.py) — the bank's round trip, MPCLoss.forward_many and
+NeuralNetwork.train_models on CPU tensors against M single-model calls, the loader helper, and the many-model entries of
+the C ABI (declared, exported, refusing bad arguments before any launch)."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import forging_control_amd as fca
+from conftest import GOLDEN, ROOT, load_case
+from forging_control_amd.many import ControllerBank, zip_loaders
+
+MANY = ("fcr_many_workspace_size", "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many",
+        "fcr_fnn_backward_many")
+FEATS = ("loss", "command", "error", "prediction")
+
+
+def seed_models(n, dtype=torch.float32):
+    """The first n of the reference's ten shipped seeds (tests/golden/ul_seed_controllers.npz) as FNNModels."""
+    w = np.load(os.path.join(GOLDEN, "ul_seed_controllers.npz"))
+    out = []
+    for i in range(n):
+        m = fca.FNNModel(3, 50, 1, 1)
+        with torch.no_grad():
+            m.fc_inp.weight.copy_(torch.as_tensor(w["W_inp"][i]))
+            m.fc_inp.bias.copy_(torch.as_tensor(w["b_inp"][i]))
+            m.fc_out.weight.copy_(torch.as_tensor(w["W_out"][i]))
+        out.append(m.to(dtype))
+    return out
+
+
+def simulator(params, dtype=torch.float32):
+    sim = fca.LSTMModel(5, params["Whh"][0].shape[1], 4, 3)
+    with torch.no_grad():
+        for k in range(3):
+            getattr(sim.lstm, f"weight_ih_l{k}").copy_(torch.as_tensor(params["Wih"][k]))
+            getattr(sim.lstm, f"weight_hh_l{k}").copy_(torch.as_tensor(params["Whh"][k]))
+        sim.fc.weight.copy_(torch.as_tensor(params["fcW"]))
+        sim.fc.bias.copy_(torch.as_tensor(params["fcb"]))
+    return sim.to(dtype)
+
+
+def stacked_inputs(M, dtype=torch.float64, seed=0):
+    """The golden B = 15 inputs, model m's a fixed perturbation of them (so the models differ in data too)."""
+    c, params = load_case("ref_b15_n10")
+    g = torch.Generator().manual_seed(seed)
+    X = torch.as_tensor(c["X"], dtype=dtype).repeat(M, 1, 1)
+    S = torch.as_tensor(c["states"], dtype=dtype).repeat(M, 1, 1, 1)
+    X = X + 0.05 * torch.randn(X.shape, generator=g, dtype=dtype) * (torch.arange(M).reshape(M, 1, 1) > 0)
+    S = S + 0.05 * torch.randn(S.shape, generator=g, dtype=dtype) * (torch.arange(M).reshape(M, 1, 1, 1) > 0)
+    return c, params, X, S
+
+
+def test_bank_round_trip_through_state_dicts():
+    torch.manual_seed(0)
+    models = [fca.FNNModel(3, 50, 1, 1) for _ in range(4)]
+    bank = ControllerBank.from_models(models)
+    assert [tuple(p.shape) for p in bank.parameters()] == [(4, 50, 3), (4, 50), (4, 50)]
+    for m, sd, back in zip(models, bank.state_dicts(), bank.to_models()):
+        fresh = fca.FNNModel(3, 50, 1, 1)
+        fresh.load_state_dict(sd)             # strict: the reference's FNNModel keys, fc_int included
+        for k, v in m.state_dict().items():
+            assert torch.equal(sd[k], v) and torch.equal(back.state_dict()[k], v), k
+    again = ControllerBank.from_models(bank.state_dicts())
+    for a, b in zip(again.state_dict().values(), bank.state_dict().values()):
+        assert torch.equal(a, b)
+    x = torch.randn(4, 7, 3)
+    u = bank(x)
+    assert u.shape == (4, 7, 1)
+    for m in range(4):
+        assert torch.allclose(u[m], models[m](x[m]), atol=1e-6)
+    with pytest.raises(ValueError):
+        ControllerBank.from_models([fca.FNNModel(3, 50, 1, 1), fca.FNNModel(3, 40, 1, 1)])
+    with pytest.raises(ValueError):
+        bank(torch.randn(3, 7, 3))
+
+
+@pytest.fixture
+def float64_default():
+    """LSTMModel's host path starts from torch.zeros states of the default dtype: fp64 modules need an fp64 default."""
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    yield
+    torch.set_default_dtype(prev)
+
+
+@pytest.mark.parametrize("noise_mode", ["none", "given", "drawn"])
+def test_forward_many_on_cpu_equals_single_calls(noise_mode, float64_default):
+    """fp64 CPU tensors: losses, features, x̂ and every gradient of forward_many equal M MPCLoss.forward calls at 1e-12
+    (noise given, and noise drawn: the draws of M successive calls, model 0 first)."""
+    M, N = 3, 4
+    c, params, X, S = stacked_inputs(M)
+    sim = simulator(params, torch.float64)
+    models = seed_models(M, torch.float64)
+    bank = ControllerBank.from_models(models)
+    B = X.shape[1]
+    noise = 0.01 * torch.randn(M, B, N, 4, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    fn = fca.MPCLoss(prediction_horizon=N, alpha=20.0)
+    w = torch.tensor([1.0, 0.5, -2.0], dtype=torch.float64)
+    kw = {"none": {}, "given": dict(enable_noise=True), "drawn": dict(enable_noise=True)}[noise_mode]
+
+    u0 = bank(X)
+    u0.retain_grad()
+    torch.manual_seed(11)
+    losses, f = fn.forward_many(sim, bank, X, u0, S, "cpu", noise=noise if noise_mode == "given" else None, **kw)
+    traj = fn.last_trajectory
+    assert fn.last_call.route == "loop" and "CPU" in fn.last_call.why
+    assert losses.shape == (M,) and traj.shape == (M, B, N, 4)
+    assert f["loss"].shape == (M, B) and f["prediction"].shape == (M, B * N)
+    (losses * w).sum().backward()
+
+    torch.manual_seed(11)
+    for m in range(M):
+        u0_m = models[m](X[m])
+        u0_m.retain_grad()
+        l, fm = fn(sim, models[m], X[m], u0_m, S[m], "cpu", noise=noise[m] if noise_mode == "given" else None, **kw)
+        (l * w[m]).backward()
+        tol = lambda a, b: float((a - b).abs().max()) <= 1e-12 * max(float(b.abs().max()), 1e-300)
+        assert tol(losses[m], l)
+        for k in FEATS:
+            assert tol(f[k][m], fm[k]), (m, k)
+        assert tol(traj[m], fn.last_trajectory), m
+        assert tol(u0.grad[m], u0_m.grad), m
+        assert tol(bank.w_inp.grad[m], models[m].fc_inp.weight.grad), m
+        assert tol(bank.b_inp.grad[m], models[m].fc_inp.bias.grad), m
+        assert tol(bank.w_out.grad[m], models[m].fc_out.weight.grad.reshape(-1)), m
+
+
+class _Loader:
+    """A list of (X, y, z) batches with the loader protocol train_model / zip_loaders use."""
+
+    def __init__(self, sizes, seed):
+        g = torch.Generator().manual_seed(seed)
+        self.batches = [(torch.rand(B, 3, generator=g) * 2 - 1, torch.zeros(B, 1), torch.rand(B, 10, 5, generator=g) * 2 - 1)
+                        for B in sizes]
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
+def test_train_models_on_cpu_equals_separate_runs():
+    """Two AdamW steps of train_models against M separate train_model runs with their own AdamW: per-model average
+    losses, features and parameters at 1e-6 (one AdamW over the bank is M independent AdamWs)."""
+    M = 3
+    _, params = load_case("ref_b15_n10")
+    sim = simulator(params)
+    for p in sim.parameters():
+        p.requires_grad_(False)
+    models = seed_models(M)
+    bank = ControllerBank.from_models(models)
+    loaders = [_Loader([5, 5], 20 + m) for m in range(M)]
+    fn = fca.MPCLoss(prediction_horizon=3, alpha=20.0)
+    opt = torch.optim.AdamW(bank.parameters(), lr=1e-3)
+    avg, feats = fca.NeuralNetwork.train_models(zip_loaders(loaders), sim, bank, fn, opt, "cpu")
+    assert len(avg) == M and feats["loss"].shape == (M, 10) and feats["prediction"].shape == (M, 30)
+    close = lambda a, b: float((a - b).abs().max()) <= 1e-6 * float(b.abs().max())
+    for m in range(M):
+        o = torch.optim.AdamW(models[m].parameters(), lr=1e-3)
+        l, f = fca.NeuralNetwork.train_model(loaders[m], sim, models[m], fn, o, "cpu")
+        assert abs(avg[m] - l) <= 1e-6 * abs(l)
+        for k in FEATS:
+            assert close(feats[k][m], f[k].detach()), (m, k)
+        assert close(bank.w_inp[m], models[m].fc_inp.weight) and close(bank.b_inp[m], models[m].fc_inp.bias)
+        assert close(bank.w_out[m], models[m].fc_out.weight.reshape(-1))
+        assert not torch.equal(bank.w_inp[m], ControllerBank.from_models(seed_models(M)).w_inp[m])   # it did move
+
+
+def test_zip_loaders_stacks_and_refuses_uneven_batches():
+    even = list(zip_loaders([_Loader([4, 2], 0), _Loader([4, 2], 1)]))
+    assert [tuple(b[0].shape) for b in even] == [(2, 4, 3), (2, 2, 3)] and even[0][2].shape == (2, 4, 10, 5)
+    with pytest.raises(ValueError, match="batch sizes differ"):
+        list(zip_loaders([_Loader([4, 2], 0), _Loader([4, 3], 1)]))
+    with pytest.raises(ValueError, match="ran out"):
+        list(zip_loaders([_Loader([4, 4], 0), _Loader([4], 1)]))
+    with pytest.raises(ValueError):
+        list(zip_loaders([]))
+
+
+def test_many_entries_are_declared_exported_and_abi_is_still_8():
+    header = open(os.path.join(ROOT, "include", "fcr.h")).read()
+    lib = fca._native.load()
+    for name in MANY:
+        assert re.search(rf"^int {name}\(", header, re.M), name
+        assert name in fca._native.EXPORTS and hasattr(lib, name), name
+    assert fca._native.ABI_VERSION == 8 and lib.fcr_abi_version() == 8
+    assert re.search(r"#define FCR_ABI_VERSION 8\b", header)
+
+
+def dims(**kw):
+    base = dict(B=15, N=10, H=50, ctrl_hidden=50, precision=0)
+    base.update(kw)
+    return fca.rollout.make_dims(base["B"], base["N"], base["H"], 3, base["ctrl_hidden"], 20.0, precision=base["precision"])
+
+
+@pytest.mark.parametrize("kw,M,limit,code,word", [
+    (dict(), -1, None, -1, "n_models"),
+    (dict(precision=1), 4, None, -4, "precision"),
+    (dict(H=64), 4, None, -4, "H=64"),
+    (dict(H=16), 4, None, -4, "H=16"),
+    (dict(B=33), 4, 32, -4, "small-batch limit"),
+    (dict(B=0), 4, None, -1, "B=0"),
+])
+def test_many_entries_refuse_bad_arguments_before_any_launch(kw, M, limit, code, word):
+    """Each refusal returns its code and a message from every rollout entry, with every pointer NULL: a call that
+    got as far as a launch would have dereferenced one."""
+    lib = fca._native.load()
+    d = dims(**kw)
+    o = fca._native.make_options(small_batch_limit=limit)
+    out = ctypes.c_size_t(0)
+    calls = {
+        "size": lambda: lib.fcr_many_workspace_size(ctypes.byref(d), ctypes.byref(o), M, 1, ctypes.byref(out)),
+        "fwd": lambda: lib.fcr_forward_many(ctypes.byref(d), ctypes.byref(o), M, None, *([None] * 10), 1, None, 0, None),
+        "bwd": lambda: lib.fcr_backward_many(ctypes.byref(d), ctypes.byref(o), M, *([None] * 8), None, 0, None),
+    }
+    for name, call in calls.items():
+        assert call() == code, name
+        assert word in lib.fcr_last_error().decode(), (name, lib.fcr_last_error().decode())
+
+
+def test_many_entries_null_pointers_and_no_op():
+    lib = fca._native.load()
+    d = dims()
+    w = fca._native.FcrWeights()
+    out = ctypes.c_size_t(0)
+    assert lib.fcr_many_workspace_size(ctypes.byref(d), None, 4, 1, None) == -1
+    assert lib.fcr_forward_many(ctypes.byref(d), None, 4, ctypes.byref(w), *([None] * 10), 1, None, 0, None) == -1
+    assert "NULL" in lib.fcr_last_error().decode()
+    assert lib.fcr_backward_many(ctypes.byref(d), None, 4, *([None] * 8), None, 0, None) == -1
+    assert "NULL" in lib.fcr_last_error().decode()
+    # n_models = 0: nothing to do, whatever the pointers
+    assert lib.fcr_forward_many(ctypes.byref(d), None, 0, None, *([None] * 10), 1, None, 0, None) == 0
+    assert lib.fcr_backward_many(ctypes.byref(d), None, 0, *([None] * 8), None, 0, None) == 0
+    assert lib.fcr_many_workspace_size(ctypes.byref(d), None, 0, 1, ctypes.byref(out)) == 0
+    # the stacked controller call
+    assert lib.fcr_fnn_forward_many(-1, 16, 3, 50, *([None] * 5), None) == -1
+    assert "n_models" in lib.fcr_last_error().decode()
+    assert lib.fcr_fnn_forward_many(4, 16, 4, 50, *([None] * 5), None) == -4
+    assert lib.fcr_fnn_forward_many(4, 16, 3, 80, *([None] * 5), None) == -4
+    assert lib.fcr_fnn_forward_many(4, 16, 3, 50, *([None] * 5), None) == -1 and "NULL" in lib.fcr_last_error().decode()
+    assert lib.fcr_fnn_forward_many(0, 16, 3, 50, *([None] * 5), None) == 0
+    assert lib.fcr_fnn_forward_many(4, 0, 3, 50, *([None] * 5), None) == 0
+    assert lib.fcr_fnn_backward_many(-1, 16, 3, 50, *([None] * 10), 0, None) == -1
+    assert lib.fcr_fnn_backward_many(4, 16, 3, 50, *([None] * 10), 0, None) == -1
+    assert lib.fcr_fnn_backward_many(0, 16, 3, 50, *([None] * 10), 0, None) == 0
+    p = ctypes.c_void_p(256)   # never dereferenced: the workspace check comes first
+    assert lib.fcr_fnn_backward_many(4, 300, 3, 50, *([p] * 10), 4 * 2 * 50 * 5 * 4 - 1, None) == -2
+
+
+def test_many_workspace_grows_with_models_and_groups():
+    n = fca._native
+    size = lambda B, M, bw=True: n.many_workspace_bytes(dims(B=B), M, bw)
+    assert size(15, 1) < size(15, 2) < size(15, 10) < size(15, 20)
+    per_group = size(15, 11) - size(15, 10)
+    # ceil(B / 16) groups per model: a row within a group adds only its x̂ / dv lines, a new group adds its slabs
+    assert size(1, 3) <= size(15, 3) <= size(16, 3) < size(17, 3) <= size(32, 3) < size(33, 3)
+    assert size(16, 3) - size(1, 3) < 0.01 * per_group and size(32, 3) - size(17, 3) < 0.01 * per_group
+    assert size(17, 3) - size(16, 3) > 0.99 * 3 * per_group and size(33, 3) - size(32, 3) > 0.99 * 3 * per_group
+    assert abs((size(15, 20) - size(15, 10)) - 10 * per_group) <= 0.01 * 10 * per_group   # 256-byte rounding of the slabs
+    assert abs((size(17, 10) - size(15, 10)) - 10 * per_group) <= 0.01 * 10 * per_group   # xhat / dv rows are the slack
+    assert size(15, 10, False) < size(15, 10) / 2
+    # a model's slabs are the single call's: 10 windows x 30 cells x 52 units of h and c per trajectory of a group
+    assert per_group > 16 * 10 * 30 * 52 * 2 * 4
