@@ -16,6 +16,7 @@
 #include "fcr_common.h"
 #include "fcr_f16.h"
 #include "fcr_img.h"
+#include "fcr_rowgrad.h"
 
 namespace fcr {
 
@@ -491,11 +492,9 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
     const float alpha = a.alpha;
     // d loss / d (one step-cost term) = dloss / (B N)   (Functions.py:1458, 1463)
     const float wgt = valid ? a.dloss[0] / ((float)a.B * (float)N) : 0.0f;
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];
     const float scq = a.p.wsc[q], sc4 = a.p.wsc[4];   // range guard (fcr_pack.h): d/dv = 2^-s_c d/dv'
     const float s84 = a.states[(size_t)bc * kL * kIn + (kL - 2) * kIn + 4];
     const float *pred = a.prediction + (size_t)bc * N;
-    const float *xh = a.xhat + (size_t)bc * N * kOut;
     const ImgLane<I1::U> L1 = img_lane<I1::U>(lds_offset(lw), lane);      // layer 2 (fp32: layers 2, 1)
     const ImgLane<I1::U> L1b = img_lane<I1::U>(lds_offset(lw1), lane);    // layer 1
     const ImgLane<I0::U> L0 = img_lane<I0::U>(lds_offset(lw0), lane);
@@ -503,12 +502,47 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
     // window-row gradients dx(w, t) (lane group q: column q; lane group 0 also column 4) go to a
     // per-wave slab; row rho = w + t of the extended sequence sums the windows that contained it.
     const __amdgpu_buffer_rsrc_t rr = wave_rsrc(a.dxrow + (size_t)wave * N * kL * kWave, (size_t)N * kL * kWave * 8);
-    auto row_grad = [&](int rho) {   // sum over windows w = max(0, rho-9) .. min(N-1, rho) of dx(w, rho-w)
+    // sum over windows w = min(N-1, rho) .. max(0, rho-9) of dx(w, rho-w), as kL fixed terms (fcr_rowgrad.h): every
+    // load is issued (row_issue) before the first add (row_sum), so the sum costs one memory latency, not one per term.
+    // A term past the row's last window loads a clamped in-range entry and adds +0.0f: the sum keeps its bits.
+    auto row_issue = [&](int rho, f32x2 (&g)[kL]) {
+#pragma unroll
+        for (int i = 0; i < kL; ++i) {
+            const RowTerm e = row_term(rho, N, i);
+            g[i] = buf_ld2(rr, lane * 8, (uint32_t)((e.w * kL + e.t) * kWave * 8));
+        }
+    };
+    auto row_sum = [&](int rho, const f32x2 (&g)[kL]) {
         f32x2 acc2 = {0.0f, 0.0f};
-        const int w_hi = rho < N - 1 ? rho : N - 1;
-        const int w_lo = rho - (kL - 1) > 0 ? rho - (kL - 1) : 0;
-        for (int w = w_hi; w >= w_lo; --w) acc2 += buf_ld2(rr, lane * 8, (uint32_t)((w * kL + (rho - w)) * kWave * 8));
+#pragma unroll
+        for (int i = 0; i < kL; ++i) {
+            const bool on = row_term(rho, N, i).valid;
+            acc2 += f32x2{on ? g[i][0] : 0.0f, on ? g[i][1] : 0.0f};
+        }
         return acc2;
+    };
+    // What a window head reads from memory (head_issue): xhat_j, the controller's reference, the row gradient's terms
+    // and pred[j .. j+2], requested in one batch (behind the refill's DMA instructions, below). Row 10+j's newest entry,
+    // (w = j+1, t = 9), was stored by the first layer-0 cell of window j+1, at least one cell earlier in this wave's
+    // program order.
+    struct HeadIn {
+        float x[kOut], p[3], ref;
+        f32x2 g[kL];
+    };
+    auto head_issue = [&](int j, int bcl, HeadIn &hi) {
+        const float *xj = a.xhat + ((size_t)bcl * N + j) * kOut, *pj = a.prediction + (size_t)bcl * N + j;
+#pragma unroll
+        for (int o = 0; o < kOut; ++o) hi.x[o] = xj[o];
+        hi.ref = a.X[(size_t)bcl * kCtrlIn + 2];
+        hi.p[0] = hi.p[1] = hi.p[2] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < kL; ++i) hi.g[i] = f32x2{0.0f, 0.0f};
+        if (j <= N - 2) {
+            row_issue(kL + j, hi.g);
+            hi.p[0] = pj[0];
+            hi.p[1] = pj[1];
+            if (j + 2 < N) hi.p[2] = pj[2];
+        }
     };
     float dh[HS], dc[HS], dxo[HS], dab[HS];
 
@@ -553,63 +587,95 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         ld_rec<HS, rec_words<HS, LP>()>(ci.c, f.rc, f.c, lane);   // (c records: f16 halves in the f16 mode)
     }
 
+    // Window turn-around: the layer-2 image refill is started (lds_fill_begin), then the head's loads go out together
+    // (head_issue), then comes the head's arithmetic, and only then is the refill awaited (lds_fill_end). The head reads
+    // only the resident lfnp, lfcp of the LDS, never the refilled region. Its loads follow the DMA instructions: this
+    // compiler waits with vmcnt(0) for any load consumed behind an LDS-DMA instruction, whatever their order, so
+    // loads issued first would not be waited for apart from the DMA anyway (profiles/turnaround_isa.log); behind it
+    // their single round trip runs beside the DMA, and the arithmetic after both is short.
+    // The head's per-lane values (lane group, trajectory, cost weights, the addresses made of them) are formed anew
+    // each window from the lane id, scalars and zj, a zero the compiler cannot see through: as loop invariants they
+    // would live across every cell, where the registers are full, i.e. in scratch, and a scratch reload issued behind
+    // the DMA is waited for behind the DMA.
+    // (what they are made of is wave-uniform and held in scalar registers: the valid lanes' wgt, and 2 alpha)
+    auto uniform = [](float v) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+    };
+    const float wgt_s = uniform(a.dloss[0] / ((float)a.B * (float)N)), alpha2_s = uniform(2.0f * alpha);
     for (int j = N - 1; j >= 0; --j) {
         const unsigned long long tw0 = stamp_now();
         const float *lfnp_j = opaque(lfnp), *lfcp_j = opaque(lfcp);
-        const float x0 = xh[j * kOut + 0], x1 = xh[j * kOut + 1], x2 = xh[j * kOut + 2],
-                    x3 = xh[j * kOut + 3];
+        const int zj = (int)(lfnp_j - lfnp);
+        struct {
+            int lane, q, sl, b;
+            bool valid;
+            float wgt, aw;
+        } hr;
+        {
+            hr.lane = lane + zj;
+            hr.q = hr.lane >> 4;
+            hr.sl = hr.lane & 15;
+            hr.b = wave * kTile + hr.sl;
+            hr.valid = hr.b < a.B;
+            hr.wgt = hr.valid ? wgt_s : 0.0f;
+            hr.aw = alpha2_s * hr.wgt;
+        }
+        const unsigned long long tw1 = stamp_now();
+        if (!LP) lds_fill_begin<I1::BYTES, kBwdWaves>(lw, a.p.img[2], hr.lane);
+        const unsigned long long tw2 = stamp_now();
+        HeadIn hin;
+        head_issue(j, hr.valid ? hr.b : a.B - 1, hin);
+        const float x0 = hin.x[0], x1 = hin.x[1], x2 = hin.x[2], x3 = hin.x[3];
         // direct cost gradients of step j (Functions.py:1443-1452)
-        float d0 = wgt * 2.0f * (x0 - ref);
-        float d1 = wgt * ((-x1 > 0.0f ? -1.0f : 0.0f) + (x1 - kP1Max > 0.0f ? 1.0f : 0.0f));
-        float d2 = wgt * ((-x2 > 0.0f ? -1.0f : 0.0f) + (x2 - kP2Max > 0.0f ? 1.0f : 0.0f));
+        float d0 = hr.wgt * 2.0f * (x0 - hin.ref);
+        float d1 = hr.wgt * ((-x1 > 0.0f ? -1.0f : 0.0f) + (x1 - kP1Max > 0.0f ? 1.0f : 0.0f));
+        float d2 = hr.wgt * ((-x2 > 0.0f ? -1.0f : 0.0f) + (x2 - kP2Max > 0.0f ? 1.0f : 0.0f));
         float d3 = 0.0f;
         if (j <= N - 2) {
             // row 10+j = (xhat_j, u_{j+1}) is complete once windows j+1 .. j+10 are done
-            const f32x2 G = row_grad(kL + j);
-            d0 += __shfl(G[0], sl);
-            d1 += __shfl(G[0], sl + 16);
-            d2 += __shfl(G[0], sl + 32);
-            d3 += __shfl(G[0], sl + 48);
-            const float g4 = __shfl(G[1], sl);
-            const float uj = pred[j], uj1 = pred[j + 1];
-            float du = 2.0f * alpha * wgt * (uj1 - uj);                       // cmd_{j+1}
-            if (j + 2 < N) du += 2.0f * alpha * wgt * (uj1 - pred[j + 2]);    // cmd_{j+2}
+            const f32x2 G = row_sum(kL + j, hin.g);
+            d0 += __shfl(G[0], hr.sl);
+            d1 += __shfl(G[0], hr.sl + 16);
+            d2 += __shfl(G[0], hr.sl + 32);
+            d3 += __shfl(G[0], hr.sl + 48);
+            const float g4 = __shfl(G[1], hr.sl);
+            const float uj = hin.p[0], uj1 = hin.p[1];
+            float du = hr.aw * (uj1 - uj);                                    // cmd_{j+1} (aw = 2 alpha wgt)
+            if (j + 2 < N) du += hr.aw * (uj1 - hin.p[2]);                    // cmd_{j+2}
             du += g4;
             // controller backward at (xhat_j[0], xhat_j[3], ref) (Functions.py:1424-1430)
             float z[kMS];
-            const float v = fnn_pre(lfnp_j, q, x0, x3, ref, z);
+            const float v = fnn_pre(lfnp_j, hr.q, x0, x3, hin.ref, z);
             const float dv = (v > -1.0f && v < 1.0f) ? du : 0.0f;            // Hardtanh'
             float dca = 0.0f, dcb = 0.0f;
 #pragma unroll
             for (int m = 0; m < kMS; ++m) {
-                const float *p = lfnp_j + (m * 4 + q) * kFnpStride;
+                const float *p = lfnp_j + (m * 4 + hr.q) * kFnpStride;
                 const float dz = (z[m] > 0.0f) ? dv * p[4] : 0.0f;               // ReLU'
                 dca += dz * p[0];
                 dcb += dz * p[1];
             }
             // the controller's parameter gradients are finished by ctrl_grad_kernel from dv
-            if (valid && q == 0) a.dv[(size_t)b * N + j] = dv;
+            if (hr.valid && hr.q == 0) a.dv[(size_t)hr.b * N + j] = dv;
             d0 += xor_sum_q(dca);
             d3 += xor_sum_q(dcb);
-        } else if (valid && q == 0) {
-            a.dv[(size_t)b * N + j] = 0.0f;   // the last step feeds no controller call
+        } else if (hr.valid && hr.q == 0) {
+            a.dv[(size_t)hr.b * N + j] = 0.0f;   // the last step feeds no controller call
         }
         // ---- layer 2: dh_9 = fc.W^T dxhat (Functions.py:377) ----
         float dh_out[HS];
 #pragma unroll
         for (int r = 0; r < HS; ++r) {
-            const float *fp = lfcp_j + r * 4 + q;
+            const float *fp = lfcp_j + r * 4 + hr.q;
             dh_out[r] = fp[0] * d0 + fp[HS * 4] * d1 + fp[2 * HS * 4] * d2 + fp[3 * HS * 4] * d3;
         }
         float unused0, unused1;
-        const unsigned long long tw1 = stamp_now();
-        if (!LP) {
-            lds_fill<I1::BYTES, kBwdWaves>(lw, a.p.img[2]);
-        }
-        if (FCR_STAMP) {
-            const unsigned long long tw2 = stamp_now();
-            sp.t[5] += tw1 - tw0;
-            sp.t[6] += tw2 - tw1;
+        const unsigned long long tw3h = stamp_now();
+        if (!LP) lds_fill_end();
+        if (FCR_STAMP) {   // head: the loads' issue and the arithmetic; fill 2: begin and end
+            const unsigned long long tw4 = stamp_now();
+            sp.t[5] += (tw1 - tw0) + (tw3h - tw2);
+            sp.t[6] += (tw2 - tw1) + (tw4 - tw3h);
         }
 #pragma unroll
         for (int r = 0; r < HS; ++r) dh[r] = dc[r] = 0.0f;
@@ -708,7 +774,9 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
             buf_st2(rr, lane * 8, (uint32_t)((j * kL) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row j
         }
     }
-    const float g_u0_rows = row_grad(kL - 1)[1];   // row 9, col 4 = u0 (Functions.py:1396)
+    f32x2 g9[kL];
+    row_issue(kL - 1, g9);
+    const float g_u0_rows = row_sum(kL - 1, g9)[1];   // row 9, col 4 = u0 (Functions.py:1396)
     // command-cost terms of u0: cmd_0 = a(s84 - u0)^2, cmd_1 = a(u0 - u1)^2
     float du0 = 2.0f * alpha * wgt * (pred[0] - s84);
     if (N > 1) du0 += 2.0f * alpha * wgt * (pred[0] - pred[1]);

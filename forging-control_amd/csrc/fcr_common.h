@@ -201,8 +201,41 @@ __device__ __forceinline__ void lds_copy(float *lw, const float *__restrict__ sr
 // Refill the per-phase LDS region with LDS-DMA (global_load_lds_dwordx4: each wave instruction moves
 // one 1 KiB chunk straight into LDS, no VGPRs): after the barrier that retires the old image, every
 // wave issues its chunks back to back; the barrier after them waits for the DMA (vmcnt) and publishes.
+// The two halves are callable apart (lds_fill_begin / lds_fill_end): between them a wave may do whatever reads
+// neither the old nor the new image — the DMA runs beside it (the fused backward's window head, fcr_bwd.h). A
+// vector-memory load consumed between the halves is waited for with vmcnt(0), i.e. together with the DMA, wherever
+// it was issued (this compiler emits no partial vmcnt across LDS-DMA instructions): work that needs loaded values
+// comes after one such wait, LDS reads of other regions and arithmetic run free.
+// `lane` (0..63, the caller's lane id) is only the per-lane part of the source address, added to a scalar chunk base:
+// a caller short of registers passes a freshly formed copy, so that no 64-bit per-lane address has to live across
+// its loop (in scratch, reloaded — and waited for — between the DMA instructions).
+template <int NBYTES, int NWAVES>
+__device__ __forceinline__ void lds_fill_begin(float *lw, const float *__restrict__ src, int lane) {
+    static_assert(NBYTES % 1024 == 0, "image must be whole 1 KiB chunks");
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    __syncthreads();
+    // A fixed, unrolled number of rounds (only the last one is conditional): straight-line DMA issue with scalar
+    // chunk bases, no loop-carried address.
+    constexpr int NCH = NBYTES / 1024, ROUNDS = (NCH + NWAVES - 1) / NWAVES;
+#pragma unroll
+    for (int k = 0; k < ROUNDS; ++k) {
+        const int c = wv + k * NWAVES;
+        if ((k + 1) * NWAVES <= NCH || c < NCH)
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void *)((const char *)src + c * 1024 + (uint32_t)(lane & 63) * 16u),
+                (__attribute__((address_space(3))) void *)((__attribute__((address_space(3))) char *)lw + c * 1024),
+                16, 0, 0);
+    }
+}
+template <int NBYTES, int NWAVES>
+__device__ __forceinline__ void lds_fill_begin(float *lw, const float *__restrict__ src) {
+    lds_fill_begin<NBYTES, NWAVES>(lw, src, (int)(threadIdx.x & 63));
+}
+__device__ __forceinline__ void lds_fill_end() { __syncthreads(); }
 template <int NBYTES, int NWAVES>
 __device__ __forceinline__ void lds_fill(float *lw, const float *__restrict__ src) {
+    // = lds_fill_begin; lds_fill_end, written out: nested in the two calls the compiler orders one address add of
+    // an unrelated kernel differently, and every caller outside the fused rollout keeps its instructions
     static_assert(NBYTES % 1024 == 0, "image must be whole 1 KiB chunks");
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     __syncthreads();
