@@ -9,11 +9,11 @@ from .functions import FNNModel, LSTMModel, MPCLoss, NeuralNetwork
 from .inference import controller_step, simulate_rollout, simulate_step, simulator_make_step
 from .plant import ForgingRK4, forging_rk4
 from .data import DeviceLoader, SequenceWindows
-from .closed_loop import ClosedLoop, FeasibilityRecovery
+from .closed_loop import ClosedLoop, ClosedLoopBank, FeasibilityRecovery
 from .graphed import CapturedStep
 from .many import ControllerBank, zip_loaders
 
 __all__ = ["FNNModel", "LSTMModel", "MPCLoss", "NeuralNetwork", "rollout", "distributed", "inference",
            "simulate_step", "simulate_rollout", "controller_step", "simulator_make_step", "plant", "ForgingRK4", "forging_rk4",
-           "data", "SequenceWindows", "DeviceLoader", "surrogate", "closed_loop", "ClosedLoop", "FeasibilityRecovery", "graphed",
+           "data", "SequenceWindows", "DeviceLoader", "surrogate", "closed_loop", "ClosedLoop", "ClosedLoopBank", "FeasibilityRecovery", "graphed",
            "CapturedStep", "launch", "supervised", "many", "ControllerBank", "zip_loaders", "_native"]

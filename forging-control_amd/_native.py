@@ -33,7 +33,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_get_small_pipe_sets", "fcr_set_wide_keep_budget", "fcr_get_wide_keep_budget", "fcr_last_error",
            "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
            "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch", "fcr_many_workspace_size",
-           "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many")
+           "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many",
+           "fcr_closed_loop_run_bank")
 LOSS_L1, LOSS_MSE = 0, 1
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
@@ -105,6 +106,18 @@ class FcrClosedLoop(ctypes.Structure):
     ]
 
 
+class FcrClosedLoopBank(ctypes.Structure):
+    """fcr_closed_loop_bank (include/fcr.h): FcrClosedLoop's fields for M stacked controllers, then the bank's own."""
+    _fields_ = FcrClosedLoop._fields_ + [
+        ("n_models", ctypes.c_int32),
+        ("x0_stride", ctypes.c_int64), ("ref_stride", ctypes.c_int64),         # elements between models; 0 = shared
+        ("process_noise_stride", ctypes.c_int64), ("meas_noise_stride", ctypes.c_int64),
+        ("p1_lo", ctypes.c_double), ("p1_hi", ctypes.c_double), ("p2_lo", ctypes.c_double), ("p2_hi", ctypes.c_double),
+        ("traj_stats", ctypes.c_void_p), ("traj_counts", ctypes.c_void_p),     # (M,B,6) fp64, (M,B,3) int32
+        ("x_final", ctypes.c_void_p), ("summary", ctypes.c_void_p),            # (M,B,5), (M,10) fp64
+    ]
+
+
 class FcrSupervised(ctypes.Structure):
     """fcr_supervised (include/fcr.h): one epoch of the supervised baseline for n_models stacked FNNModels."""
     _fields_ = [
@@ -171,6 +184,8 @@ def load() -> ctypes.CDLL:
         lib.fcr_lstm_rollout.restype = i32
         lib.fcr_closed_loop_run.argtypes = [ctypes.POINTER(FcrClosedLoop), vp]
         lib.fcr_closed_loop_run.restype = i32
+        lib.fcr_closed_loop_run_bank.argtypes = [ctypes.POINTER(FcrClosedLoopBank), vp]   # a pure addition to ABI 8
+        lib.fcr_closed_loop_run_bank.restype = i32
         lib.fcr_feasibility_project.argtypes = [ctypes.POINTER(FcrFeasibility), i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_feasibility_project.restype = i32
         lib.fcr_supervised_epoch.argtypes = [ctypes.POINTER(FcrSupervised), vp]

@@ -15,7 +15,9 @@ one more launch (``fcr_lstm_rollout``, csrc/fcr_lstm_rollout.h). The reference's
 (``FeasibilityRecovery.feasibility_recover``, a CasADi/IPOPT solve per step) is :class:`FeasibilityRecovery`: its
 NLP is the projection of one command onto the set that keeps both pressures inside their bounds over the next two
 steps, which ``csrc/fcr_feasibility.h`` searches on the GPU, alone (``project``) or inside the loop's launch
-(``feasibility=``).
+(``feasibility=``). :class:`ClosedLoopBank` runs the M controllers of a ``ControllerBank`` through that loop in one
+launch (``fcr_closed_loop_run_bank``) and returns the evaluation's numbers — the reference's ``metrics`` /
+``other_metrics`` (Functions.py:751-822), command smoothness and constraint violation — accumulated in the loop kernel.
 """
 from __future__ import annotations
 
@@ -195,27 +197,164 @@ class ClosedLoop:
         commands, which also drive the surrogate's track (Functions.py:1196), and ``results`` gains ``u_nn`` and
         ``feas_flag`` (B,T)."""
         x, u, *info = self.run(x0, ref, process_noise, meas_noise, feasibility)
-        dev = x.device
-        s_in, s_out = _scale(model_scalers["input"]), _scale(model_scalers["output"])
-        if s_in.shape != (5,) or s_out.shape != (4,):
-            raise ValueError(f"model_scalers: 'input' needs 5 scales and 'output' 4, got {s_in.shape[0]} and "
-                             f"{s_out.shape[0]}")
-        B, T = u.shape
+        s_in, s_out = _model_scales(model_scalers)
         results = {"y": x[:, :, 0], "y_dot": x[:, :, 1], "p1": x[:, :, 2], "p2": x[:, :, 3], "z": x[:, :, 4],
                    "ref": ref.to(torch.float64), "u": u}
         if info:
             results["u_nn"], results["feas_flag"] = info[0]["u_nn"], info[0]["flag"]
-        first = x[:, 0, 1:5]
-        track = torch.empty(B, T + 1, 4, dtype=torch.float64, device=dev)
-        track[:, 0] = first
-        if T > 0:
-            t_in = torch.tensor(s_in, dtype=torch.float64, device=dev)
-            t_out = torch.tensor(s_out, dtype=torch.float64, device=dev)
-            # the t = 0 window: [x0[1:5], u_0] scaled, repeated over the lookback rows (Functions.py:1196-1203)
-            row0 = (torch.cat([first, u[:, :1]], dim=1) / t_in).to(torch.float32)
-            window0 = row0[:, None, :].expand(B, 10, 5).contiguous()
-            cmd = (u / t_in[4]).to(torch.float32)
-            xhat = simulate_rollout(simulator, window0, cmd, gain=s_out / s_in[:4], noise=lstm_noise)
-            track[:, 1:] = xhat.to(torch.float64) * t_out
+        track = _shadow_track(x[:, 0, 1:5], u, simulator, s_in, s_out, lstm_noise)
         results_lstm = {"y_dot": track[:, :, 0], "p1": track[:, :, 1], "p2": track[:, :, 2], "z": track[:, :, 3]}
+        return results, results_lstm
+
+
+def _model_scales(model_scalers: dict):
+    s_in, s_out = _scale(model_scalers["input"]), _scale(model_scalers["output"])
+    if s_in.shape != (5,) or s_out.shape != (4,):
+        raise ValueError(f"model_scalers: 'input' needs 5 scales and 'output' 4, got {s_in.shape[0]} and "
+                         f"{s_out.shape[0]}")
+    return s_in, s_out
+
+
+def _shadow_track(first: torch.Tensor, u: torch.Tensor, simulator, s_in, s_out, lstm_noise):
+    """The surrogate's track (Functions.py:1196-1231) for R rows: ``first (R,4)`` = x0[:,1:5], ``u (R,T)`` the applied
+    commands -> ``(R,T+1,4)`` fp64, row 0 = ``first``; one ``simulate_rollout`` launch."""
+    dev = u.device
+    B, T = u.shape
+    track = torch.empty(B, T + 1, 4, dtype=torch.float64, device=dev)
+    track[:, 0] = first
+    if T > 0:
+        t_in = torch.tensor(s_in, dtype=torch.float64, device=dev)
+        t_out = torch.tensor(s_out, dtype=torch.float64, device=dev)
+        # the t = 0 window: [x0[1:5], u_0] scaled, repeated over the lookback rows (Functions.py:1196-1203)
+        row0 = (torch.cat([first, u[:, :1]], dim=1) / t_in).to(torch.float32)
+        window0 = row0[:, None, :].expand(B, 10, 5).contiguous()
+        cmd = (u / t_in[4]).to(torch.float32)
+        xhat = simulate_rollout(simulator, window0, cmd, gain=s_out / s_in[:4], noise=lstm_noise)
+        track[:, 1:] = xhat.to(torch.float64) * t_out
+    return track
+
+
+METRIC_KEYS = ("MAE", "RMSE", "R2", "max_err", "Command", "du_rms", "viol_max", "viol_frac", "flag1_frac", "flag2_frac")
+
+
+class ClosedLoopBank:
+    """:class:`ClosedLoop` for the M controllers of a :class:`~.many.ControllerBank` (one hidden width, one set of
+    scalers): M x B trajectories over T steps in ONE launch (``fcr_closed_loop_run_bank``), and the numbers the
+    reference tabulates per seed (``metrics`` / ``other_metrics``, Functions.py:751-822) from the same launch plus one
+    small reduction. Model m's trajectories are ``ClosedLoop(controller_m).run(...)``'s on model m's inputs, bit for bit.
+
+    ``run`` returns a dict:
+
+    * ``x (M,B,T+1,5)``, ``u (M,B,T)`` and, under ``feasibility``, ``u_nn (M,B,T)``, ``flag (M,B,T)`` int32 — or ``None``
+      each with ``store=False`` (nothing is stored per step; ``u_nn`` and ``flag`` are ``None`` without recovery);
+    * ``x_final (M,B,5)``: the unperturbed state after step T;
+    * ``traj_stats (M,B,6)`` fp64: per trajectory, with e = ``x[:,t+1,1] - ref[:,t]`` (the record as stored, measurement
+      noise included), sum |e|, sum e^2, max |e|, sum |u|, sum_{t>=1} (u_t - u_{t-1})^2, and the worst violation
+      max_t max(p1_lo - p1, p1 - p1_hi, p2_lo - p2, p2 - p2_hi) of the records' pressures (Pa);
+    * ``traj_counts (M,B,3)`` int32: steps with violation > 0, steps flagged 1, steps flagged 2;
+    * ``metrics``: ``(M,)`` fp64 tensors keyed ``MAE``, ``RMSE``, ``R2``, ``Command`` (the reference's ``results_dict``
+      keys; speed tracking over all B*T steps, mean |u|), ``max_err``, ``du_rms``, ``viol_max``, ``viol_frac``,
+      ``flag1_frac``, ``flag2_frac``."""
+
+    def __init__(self, bank, scalers: dict, ts: float = TS_REFERENCE, substeps: int = SUBSTEPS_REFERENCE,
+                 smooth: bool = True):
+        for name in ("w_inp", "b_inp", "w_out"):
+            if not hasattr(bank, name):
+                raise TypeError(f"ClosedLoopBank needs a ControllerBank (stacked w_inp, b_inp, w_out); got {type(bank).__name__}")
+        self.bank = bank
+        s_in = _scale(scalers["input"])
+        self.in_scale = (float(s_in[0]), float(s_in[1]))
+        self.ref_scale = float(_scale(scalers["y_dot"])[0])
+        self.out_scale = float(_scale(scalers["output"])[0])
+        self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
+
+    @staticmethod
+    def _per_model(name, t, M, tail):
+        """Whether ``t`` is ``(M,) + tail`` (True) or ``tail``, one copy shared by all models (False)."""
+        if tuple(t.shape) == tail:
+            return False
+        if tuple(t.shape) == (M,) + tail:
+            return True
+        raise ValueError(f"{name} must be {tail} (shared by all models) or {(M,) + tail}, got {tuple(t.shape)}")
+
+    def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
+            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
+            p_bounds=None):
+        """``x0 (B,5)`` or ``(M,B,5)``, ``ref (B,T)`` or ``(M,B,T)``, each noise ``(B,T,5)`` or ``(M,B,T,5)``: without
+        the leading M one copy is shared by all models (and read once from memory, not expanded). ``p_bounds``:
+        ``((p1_lo, p1_hi), (p2_lo, p2_hi))`` in Pa for the violation statistics; default the ``feasibility``'s own
+        bounds, otherwise 0 and 32e6. ``store=False`` skips every per-step store; the statistics, ``x_final`` and
+        ``metrics`` are the storing run's bit for bit."""
+        M = self.bank.w_inp.shape[0]
+        if x0.dim() not in (2, 3) or x0.shape[-1] != 5 or ref.dim() not in (2, 3):
+            raise ValueError(f"x0 must be (B,5) or (M,B,5) and ref (B,T) or (M,B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
+        B, T = x0.shape[-2], ref.shape[-1]
+        stacked = {"x0": self._per_model("x0", x0, M, (B, 5)), "ref": self._per_model("ref", ref, M, (B, T))}
+        for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
+            stacked[name] = n is not None and self._per_model(name, n, M, (B, T, 5))
+        dev = x0.device
+        if dev.type != "cuda" or ref.device != dev:
+            raise RuntimeError(f"ClosedLoopBank runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
+        for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
+            if n is not None and n.device != dev:
+                raise RuntimeError(f"{name} must be on {dev}, found it on {n.device}")
+        if p_bounds is None:
+            p_bounds = (feasibility.p1, feasibility.p2) if feasibility is not None else ((0.0, 32e6), (0.0, 32e6))
+        (p1_lo, p1_hi), (p2_lo, p2_hi) = p_bounds
+        f64 = lambda t: None if t is None else t.to(torch.float64).contiguous()
+        x0c, refc, wc, vc = f64(x0), f64(ref), f64(process_noise), f64(meas_noise)
+        W_inp, b_inp, W_out = (p.detach().to(device=dev, dtype=torch.float32).contiguous()
+                               for p in (self.bank.w_inp, self.bank.b_inp, self.bank.w_out))
+        new = lambda *shape, dtype=torch.float64: torch.empty(*shape, dtype=dtype, device=dev)
+        out = {"x": new(M, B, T + 1, 5) if store else None, "u": new(M, B, T) if store else None, "u_nn": None, "flag": None}
+        f_struct = None
+        if feasibility is not None:
+            f_struct = feasibility.struct()                  # stays alive over the call below
+            if store:
+                out["u_nn"], out["flag"] = new(M, B, T), new(M, B, T, dtype=torch.int32)
+        out["x_final"], out["traj_stats"] = new(M, B, 5), new(M, B, 6)
+        out["traj_counts"] = new(M, B, 3, dtype=torch.int32)
+        summary = new(M, 10)
+        p = lambda t: None if t is None else t.data_ptr()
+        stride = lambda name, per: per if stacked[name] else 0
+        args = _native.FcrClosedLoopBank(
+            B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp), p(b_inp), p(W_out), W_inp.shape[1],
+            (ctypes.c_double * 2)(*self.in_scale), self.ref_scale, self.out_scale, p(out["x"]), p(out["u"]), p(wc), p(vc),
+            None if f_struct is None else ctypes.pointer(f_struct), p(out["u_nn"]), p(out["flag"]), M,
+            stride("x0", B * 5), stride("ref", B * T), stride("process_noise", B * T * 5), stride("meas_noise", B * T * 5),
+            float(p1_lo), float(p1_hi), float(p2_lo), float(p2_hi), p(out["traj_stats"]), p(out["traj_counts"]),
+            p(out["x_final"]), p(summary))
+        _native.check(_native.load().fcr_closed_loop_run_bank(
+            ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "fcr_closed_loop_run_bank")
+        if M == 0 or B == 0:
+            summary.zero_()
+        out["metrics"] = {k: summary[:, i] for i, k in enumerate(METRIC_KEYS)}
+        return out
+
+    def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
+             process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
+             lstm_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
+             p_bounds=None):
+        """:meth:`ClosedLoop.loop` for every model: ``(results, results_LSTM)`` keyed as there, every tensor with a
+        leading model dimension (``ref`` expanded to ``(M,B,T)``), plus ``results['metrics']``. The surrogate is shared
+        by the models, so its track is ONE ``simulate_rollout`` launch on the ``(M*B)`` stack of rows. ``lstm_noise``:
+        ``(B,T,4)`` shared or ``(M,B,T,4)``. The tracks are built from the stored trajectories: ``store`` must be True."""
+        if not store:
+            raise ValueError("ClosedLoopBank.loop builds both tracks from the stored trajectories: store=True is required")
+        s_in, s_out = _model_scales(model_scalers)
+        r = self.run(x0, ref, process_noise, meas_noise, feasibility, True, p_bounds)
+        x, u = r["x"], r["u"]
+        M, B, T = u.shape
+        results = {"y": x[..., 0], "y_dot": x[..., 1], "p1": x[..., 2], "p2": x[..., 3], "z": x[..., 4],
+                   "ref": ref.to(torch.float64).expand(M, B, T), "u": u, "metrics": r["metrics"]}
+        if feasibility is not None:
+            results["u_nn"], results["feas_flag"] = r["u_nn"], r["flag"]
+        if lstm_noise is not None:
+            if self._per_model("lstm_noise", lstm_noise, M, (B, T, 4)):
+                lstm_noise = lstm_noise.reshape(M * B, T, 4)
+            else:
+                lstm_noise = lstm_noise.expand(M, B, T, 4).reshape(M * B, T, 4)
+        track = _shadow_track(x[:, :, 0, 1:5].reshape(M * B, 4), u.reshape(M * B, T), simulator, s_in, s_out, lstm_noise)
+        track = track.reshape(M, B, T + 1, 4)
+        results_lstm = {"y_dot": track[..., 0], "p1": track[..., 1], "p2": track[..., 2], "z": track[..., 3]}
         return results, results_lstm

@@ -158,6 +158,17 @@ struct ProjectedCommand {
         flag[t] = r.flag;
         return r.u;
     }
+    // as called under closed_loop::LaneStats: the stores are optional, the flag goes to the lane's counts
+    __device__ __forceinline__ double operator()(const double (&m)[5], double un, int t, bool store, int &fl) const {
+        const Projected r = project(m, un, f);
+        if (store) {
+            u_nn[t] = un;
+            u[t] = r.u;
+            flag[t] = r.flag;
+        }
+        fl = r.flag;
+        return r.u;
+    }
 };
 
 template <bool SMOOTH, bool NOISE>
@@ -165,6 +176,15 @@ __global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_recover_ker
                                                                                     const double *wn, const double *vn,
                                                                                     double *u_nn, int32_t *flag) {
     closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand{f, a.u, u_nn, flag});
+}
+
+// closed_loop_bank_kernel with recovery: u_nn and flag are model-major like a.u, and null with it.
+template <bool SMOOTH, bool NOISE, bool STORE>
+__global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_bank_recover_kernel(
+    closed_loop::ClArgs a, FeasArgs f, closed_loop::BankStrides strides, closed_loop::StatsArgs stats, const double *wn,
+    const double *vn, double *u_nn, int32_t *flag) {
+    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand{f, a.u, u_nn, flag},
+                                          closed_loop::BankModel(a.B, strides), closed_loop::LaneStats<STORE>(stats));
 }
 
 }  // namespace feasibility

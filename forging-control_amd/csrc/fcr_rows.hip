@@ -134,6 +134,76 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
     return launch_check(recover ? "closed_loop_recover_kernel" : (noise ? "closed_loop_noise_kernel" : "closed_loop_kernel"));
 }
 
+int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *c, void *stream) {
+    const char *who = "fcr_closed_loop_run_bank";
+    if (!c) return fail(FCR_EINVAL, "%s: args is NULL", who);
+    if (c->n_models < 0) return fail(FCR_EINVAL, "%s: n_models=%d must be >= 0", who, c->n_models);
+    if (c->B < 0 || c->T < 0) return fail(FCR_EINVAL, "%s: B=%d, T=%d must be >= 0", who, c->B, c->T);
+    if (const int rc = check_step(who, "", c->ts, c->substeps)) return rc;
+    if (c->smooth != 0 && c->smooth != 1) return fail(FCR_EINVAL, "%s: smooth=%d must be 0 or 1", who, c->smooth);
+    if (c->ctrl_hidden < 1 || c->ctrl_hidden > closed_loop::kClMaxHidden)
+        return fail(FCR_EUNSUPPORTED, "%s: ctrl_hidden=%d: built for 1..%d", who, c->ctrl_hidden, closed_loop::kClMaxHidden);
+    if (!(c->in_scale[0] > 0.0) || !(c->in_scale[1] > 0.0) || !(c->ref_scale > 0.0) || !(c->out_scale > 0.0))
+        return fail(FCR_EINVAL, "%s: scaler scales must be positive", who);
+    if (!(c->p1_lo < c->p1_hi) || !(c->p2_lo < c->p2_hi))
+        return fail(FCR_EINVAL, "%s: pressure bounds p1 [%g, %g], p2 [%g, %g] need lo < hi", who, c->p1_lo, c->p1_hi,
+                    c->p2_lo, c->p2_hi);
+    if (c->x0_stride < 0 || c->ref_stride < 0 || c->process_noise_stride < 0 || c->meas_noise_stride < 0)
+        return fail(FCR_EINVAL, "%s: a model stride is negative", who);
+    feasibility::FeasArgs fa{};
+    if (c->feasibility)
+        if (const int rc = feasibility_args(who, c->feasibility, &fa)) return rc;
+    const long long bpm = ((long long)c->B + closed_loop::kClBlock - 1) / closed_loop::kClBlock;
+    if (c->n_models * bpm > INT32_MAX || (long long)c->n_models * c->B * ((long long)c->T + 1) * 5 > (1LL << 40))
+        return fail(FCR_EINVAL, "%s: n_models*B*(T+1) too large", who);
+    if (c->n_models == 0 || c->B == 0) return FCR_OK;
+    if (!c->x0 || !c->ctrl_w_inp || !c->ctrl_b_inp || !c->ctrl_w_out || !c->traj_stats || !c->traj_counts || !c->x_final ||
+        !c->summary || (c->T > 0 && !c->ref))
+        return fail(FCR_EINVAL, "%s: a required pointer is NULL", who);
+    const bool recover = c->T > 0 && c->feasibility;
+    if (c->x ? (c->T > 0 && (!c->u || (recover && (!c->u_nn || !c->feas_flag)))) : (c->u || c->u_nn || c->feas_flag))
+        return fail(FCR_EINVAL, "%s: x, u (and u_nn, feas_flag with feasibility) are stored together: all set, or all NULL "
+                                "to store nothing per step", who);
+    if ((((uintptr_t)c->x0) | ((uintptr_t)c->ref) | ((uintptr_t)c->x) | ((uintptr_t)c->u) | ((uintptr_t)c->u_nn) |
+         ((uintptr_t)c->process_noise) | ((uintptr_t)c->meas_noise) | ((uintptr_t)c->traj_stats) | ((uintptr_t)c->x_final) |
+         ((uintptr_t)c->summary)) & 7)
+        return fail(FCR_EINVAL, "%s: fp64 buffers must be 8-byte aligned", who);
+    if ((((uintptr_t)c->feas_flag) | ((uintptr_t)c->traj_counts) | ((uintptr_t)c->ctrl_w_inp) | ((uintptr_t)c->ctrl_b_inp) |
+         ((uintptr_t)c->ctrl_w_out)) & 3)
+        return fail(FCR_EINVAL, "%s: int32 and fp32 buffers must be 4-byte aligned", who);
+    closed_loop::ClArgs a{c->B, c->T, c->substeps, c->ctrl_hidden, c->ts / c->substeps, c->x0, c->ref,
+                          c->ctrl_w_inp, c->ctrl_b_inp, c->ctrl_w_out, c->in_scale[0], c->in_scale[1],
+                          c->ref_scale, c->out_scale, c->x, c->u};
+    const closed_loop::BankStrides st{c->x0_stride, c->ref_stride, c->process_noise_stride, c->meas_noise_stride};
+    const closed_loop::StatsArgs sa{c->p1_lo, c->p1_hi, c->p2_lo, c->p2_hi, c->traj_stats, c->traj_counts, c->x_final};
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)(c->n_models * bpm)), block(closed_loop::kClBlock);
+    // the single-model call's choice of instantiation; T = 0 copies x0 and writes zero statistics
+    const bool sm = c->smooth, noise = c->T > 0 && (c->process_noise || c->meas_noise), store = c->x != nullptr;
+    if (recover) {
+        using feasibility::closed_loop_bank_recover_kernel;
+        static constexpr decltype(&closed_loop_bank_recover_kernel<false, false, false>) k[2][2][2] = {
+            {{closed_loop_bank_recover_kernel<false, false, false>, closed_loop_bank_recover_kernel<false, false, true>},
+             {closed_loop_bank_recover_kernel<false, true, false>, closed_loop_bank_recover_kernel<false, true, true>}},
+            {{closed_loop_bank_recover_kernel<true, false, false>, closed_loop_bank_recover_kernel<true, false, true>},
+             {closed_loop_bank_recover_kernel<true, true, false>, closed_loop_bank_recover_kernel<true, true, true>}}};
+        hipLaunchKernelGGL(k[sm][noise][store], grid, block, 0, s, a, fa, st, sa, c->process_noise, c->meas_noise, c->u_nn,
+                           c->feas_flag);
+    } else {
+        using closed_loop::closed_loop_bank_kernel;
+        static constexpr decltype(&closed_loop_bank_kernel<false, false, false>) k[2][2][2] = {
+            {{closed_loop_bank_kernel<false, false, false>, closed_loop_bank_kernel<false, false, true>},
+             {closed_loop_bank_kernel<false, true, false>, closed_loop_bank_kernel<false, true, true>}},
+            {{closed_loop_bank_kernel<true, false, false>, closed_loop_bank_kernel<true, false, true>},
+             {closed_loop_bank_kernel<true, true, false>, closed_loop_bank_kernel<true, true, true>}}};
+        hipLaunchKernelGGL(k[sm][noise][store], grid, block, 0, s, a, st, sa, c->process_noise, c->meas_noise);
+    }
+    if (const int rc = launch_check(recover ? "closed_loop_bank_recover_kernel" : "closed_loop_bank_kernel")) return rc;
+    const closed_loop::RedArgs ra{c->B, c->T, c->ref_stride, c->ref, c->traj_stats, c->traj_counts, c->summary};
+    hipLaunchKernelGGL(closed_loop::loop_stats_reduce_kernel, dim3(c->n_models), dim3(closed_loop::kRedBlock), 0, s, ra);
+    return launch_check("loop_stats_reduce_kernel");
+}
+
 int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,
                             int32_t *flag, double *v, void *stream) {
     if (!f) return fail(FCR_EINVAL, "fcr_feasibility_project: parameters is NULL");

@@ -290,6 +290,56 @@ int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x
                             int32_t *flag, double *v, void *stream);
 
 /*
+ * The closed loop for a bank of M controllers, with the evaluation's numbers (a pure addition to ABI 8): what the
+ * reference repeats per seed — NeuralNetwork.loop, then metrics / other_metrics (Functions.py:751-822) — for n_models
+ * controllers × B trajectories × T steps in one launch plus one small reduction. The fields up to feas_flag are
+ * fcr_closed_loop's and mean the same, except:
+ *   ctrl_w_inp (M,hidden,3), ctrl_b_inp (M,hidden), ctrl_w_out (M,hidden): the stacked controllers (one hidden width,
+ *     one set of scalers);
+ *   x0, ref, process_noise, meas_noise: model m reads from base + m * stride ELEMENTS (x0_stride = B*5 for (M,B,5),
+ *     0 for one (B,5) shared by all models, and so on);
+ *   outputs are model-major: x (M,B,T+1,5), u, u_nn (M,B,T), feas_flag (M,B,T) int32. Model m's rows are what
+ *     fcr_closed_loop_run returns for controller m on model m's inputs, bit for bit;
+ *   storing is optional: x = NULL skips every per-step store, and then u, u_nn and feas_flag must be NULL too.
+ * Always written, once after the loop (t = 0..T-1, r = ref[b,t], (y, p1, p2) from the record x[:,t+1] as stored,
+ * measurement noise included, u the applied command):
+ *   traj_stats  (M,B,6) fp64   sum |y-r|, sum (y-r)^2, max |y-r|, sum |u|, sum_{t>=1} (u_t - u_{t-1})^2, and the worst
+ *                              violation max_t max(p1_lo - p1, p1 - p1_hi, p2_lo - p2, p2 - p2_hi) in Pa
+ *   traj_counts (M,B,3) int32  steps with violation > 0, steps flagged 1, steps flagged 2 (0 without feasibility)
+ *   x_final     (M,B,5) fp64   the unperturbed state after step T
+ *   summary     (M,10)  fp64   over n = B*T: MAE, RMSE, R2 = 1 - SSE/SST (SST = sum (r - mean r)^2, mean first), max |e|,
+ *                              mean |u|, RMS of du over B*(T-1) terms (0 at T = 1), the worst violation, and the fractions
+ *                              of steps violating, flagged 1, flagged 2. Fixed summation order: same call, same bits.
+ * p1_lo .. p2_hi are the bounds the violation is measured against (lo < hi); they need not be the feasibility's.
+ * n_models = 0 and B = 0 are no-ops; T = 0 copies x0 (into x unless NULL, and x_final) and writes zero statistics.
+ * Stream-ordered; nothing allocates or synchronises.
+ */
+typedef struct fcr_closed_loop_bank {
+    int32_t B, T;
+    double ts;
+    int32_t substeps, smooth;
+    const double *x0, *ref;
+    const float *ctrl_w_inp, *ctrl_b_inp, *ctrl_w_out;
+    int32_t ctrl_hidden;
+    double in_scale[2];
+    double ref_scale, out_scale;
+    double *x, *u;
+    const double *process_noise, *meas_noise;
+    const fcr_feasibility *feasibility;
+    double *u_nn;
+    int32_t *feas_flag;
+    int32_t n_models;
+    int64_t x0_stride, ref_stride, process_noise_stride, meas_noise_stride;
+    double p1_lo, p1_hi, p2_lo, p2_hi;
+    double *traj_stats;
+    int32_t *traj_counts;
+    double *x_final;
+    double *summary;
+} fcr_closed_loop_bank;
+
+int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *args, void *stream);
+
+/*
  * Training-sample windows: the tables of the concatenated per-trajectory
  * SequenceDatasets (Functions.py:92-132, built by Data.get_individual_dataset :479-516 and
  * ConcatDataset, UL/Main.py:270-279), resident in device memory.
