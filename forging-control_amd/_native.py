@@ -34,7 +34,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_abi_version", "fcr_wide_bwd_cell_workspace", "fcr_wide_bwd_cell", "fcr_lstm_rollout_workspace_size",
            "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch", "fcr_many_workspace_size",
            "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many",
-           "fcr_closed_loop_run_bank")
+           "fcr_closed_loop_run_bank", "fcr_press_nominal", "fcr_plant_rk4_press", "fcr_feasibility_project_press",
+           "fcr_closed_loop_run_bank_press")
 LOSS_L1, LOSS_MSE = 0, 1
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
@@ -118,6 +119,13 @@ class FcrClosedLoopBank(ctypes.Structure):
     ]
 
 
+class FcrPress(ctypes.Structure):
+    """fcr_press (include/fcr.h): the press and the workpiece, one row of a parameter table."""
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "m_mass", "b_damp", "ft", "d1", "d2", "g", "kb", "v1_0", "v2_0", "kl_1", "kl_2", "cd", "rho", "d", "ps", "pt",
+        "mu", "k", "w0", "h0", "b0", "t_def", "t1", "m0", "m1", "m2", "m3", "m4")]
+
+
 class FcrSupervised(ctypes.Structure):
     """fcr_supervised (include/fcr.h): one epoch of the supervised baseline for n_models stacked FNNModels."""
     _fields_ = [
@@ -188,6 +196,19 @@ def load() -> ctypes.CDLL:
         lib.fcr_closed_loop_run_bank.restype = i32
         lib.fcr_feasibility_project.argtypes = [ctypes.POINTER(FcrFeasibility), i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_feasibility_project.restype = i32
+        # the press as data (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the addition
+        # (an A/B timing against an earlier commit) loads without it; the press calls then raise AttributeError.
+        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_press_nominal"):
+            lib.fcr_press_nominal.argtypes = [ctypes.POINTER(FcrPress)]
+            lib.fcr_press_nominal.restype = None
+            lib.fcr_plant_rk4_press.argtypes = [i32, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
+            lib.fcr_plant_rk4_press.restype = i32
+            lib.fcr_feasibility_project_press.argtypes = [ctypes.POINTER(FcrFeasibility), ctypes.POINTER(FcrPress), i32,
+                                                          vp, vp, vp, vp, vp, vp]
+            lib.fcr_feasibility_project_press.restype = i32
+            lib.fcr_closed_loop_run_bank_press.argtypes = [ctypes.POINTER(FcrClosedLoopBank), vp, ctypes.c_int64,
+                                                           ctypes.c_int64, ctypes.POINTER(FcrPress), vp]
+            lib.fcr_closed_loop_run_bank_press.restype = i32
         lib.fcr_supervised_epoch.argtypes = [ctypes.POINTER(FcrSupervised), vp]
         lib.fcr_supervised_epoch.restype = i32
         lib.fcr_window_gather.argtypes = [ctypes.POINTER(FcrWindows), i32, vp, vp, vp, vp, vp, vp]

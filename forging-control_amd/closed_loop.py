@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes
 import random
+import types
 
 import numpy as np
 import torch
@@ -30,7 +31,7 @@ import torch
 from . import _native
 from .functions import _controller_params
 from .inference import simulate_rollout
-from .plant import SUBSTEPS_REFERENCE, TS_REFERENCE
+from .plant import SUBSTEPS_REFERENCE, TS_REFERENCE, PressParams, as_press_table
 
 
 def tvp_fun(t_now: float, ref_step: float, bias_work: int, bias_return: int, epsilon: float = 1e-7) -> float:
@@ -83,10 +84,20 @@ class FeasibilityRecovery:
     feasible command found by probing ``u_nn -/+ (u_hi - u_lo)/2^expand * 2^k`` (clipped to ``u_bounds``) for
     k = 0..expand and bisecting ``bisect`` times towards ``u_nn``; 2 = no probe is feasible and ``u`` is
     ``clip(u_nn, *u_bounds)``, the reference's ``except`` branch. The search returns the nearest feasible command
-    wherever the feasible set is an interval on the probed side."""
+    wherever the feasible set is an interval on the probed side.
+
+    ``model_params``: the press the projection's MODEL integrates — a :class:`~.plant.PressParams` or a ``(28,)`` row,
+    one set per call; ``None`` is the reference's press, the projection as it always was. Inside a loop it is the
+    controller's idea of the press and need not be the press the loop steps (``plant_params`` there)."""
 
     def __init__(self, p1=(0.0, 32e6), p2=(0.0, 32e6), u_bounds=(-0.2, 0.2), ts: float = TS_REFERENCE,
-                 substeps: int = SUBSTEPS_REFERENCE, expand: int = 10, bisect: int = 30):
+                 substeps: int = SUBSTEPS_REFERENCE, expand: int = 10, bisect: int = 30, model_params=None):
+        if model_params is not None and not isinstance(model_params, PressParams):
+            row = np.asarray(torch.as_tensor(model_params).cpu(), dtype=np.float64)
+            if row.shape != (28,):
+                raise ValueError(f"model_params must be a PressParams or a (28,) row, got shape {row.shape}")
+            model_params = PressParams(*row.tolist())
+        self.model_params = model_params
         self.p1, self.p2 = (float(p1[0]), float(p1[1])), (float(p2[0]), float(p2[1]))
         self.u_bounds = (float(u_bounds[0]), float(u_bounds[1]))
         self.ts, self.substeps, self.expand, self.bisect = float(ts), int(substeps), int(expand), int(bisect)
@@ -108,6 +119,13 @@ class FeasibilityRecovery:
         flag = torch.empty(B, dtype=torch.int32, device=dev)
         v = torch.empty(B, dtype=torch.float64, device=dev) if return_violation else None
         f = self.struct()
+        if self.model_params is not None:
+            model = self.model_params.struct()
+            _native.check(_native.load().fcr_feasibility_project_press(
+                ctypes.byref(f), ctypes.byref(model), B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
+                None if v is None else v.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                "fcr_feasibility_project_press")
+            return (u, flag, v) if return_violation else (u, flag)
         _native.check(_native.load().fcr_feasibility_project(
             ctypes.byref(f), B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
             None if v is None else v.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
@@ -123,8 +141,9 @@ class ClosedLoop:
     [y_dot, z, ref]; the first two are used), ``'y_dot'`` (scales the reference) and ``'output'``."""
 
     def __init__(self, controller, scalers: dict, ts: float = TS_REFERENCE, substeps: int = SUBSTEPS_REFERENCE,
-                 smooth: bool = True):
+                 smooth: bool = True, plant_params=None):
         self.controller = controller
+        self.plant_params = plant_params                     # the default of run(plant_params=...)
         s_in = _scale(scalers["input"])
         self.in_scale = (float(s_in[0]), float(s_in[1]))
         self.ref_scale = float(_scale(scalers["y_dot"])[0])
@@ -132,7 +151,7 @@ class ClosedLoop:
         self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
-            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None):
+            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, plant_params=None):
         """``process_noise`` / ``meas_noise``: (B,T,5) pre-drawn ``w0`` / ``v0`` (:func:`harness_noise`), or None.
         ``w`` is in the units of x_dot and is held over the step: every RK4 stage evaluates f(x,u) + w[b,t].
         ``x[:,t+1]`` records x_{t+1} + v[b,t]; the controller reads that record, the press integrates on from the
@@ -143,7 +162,25 @@ class ClosedLoop:
         state the controller reads (under ``meas_noise`` the noisy record) and steps the press with the projected
         command. The call then returns ``(x, u, info)``: ``u`` the projected commands, ``info = {"u_nn": (B,T) the
         controller's raw commands, "flag": (B,T) int32 the projection's flags}``. With ``None`` it returns ``(x, u)``
-        as it always did."""
+        as it always did.
+
+        ``plant_params``: the press the loop steps — a :class:`~.plant.PressParams` or ``(28,)`` row for all
+        trajectories, or a ``(B,28)`` table, one row per trajectory; ``None``: the constructor's, by default the
+        reference's press. With parameters (here or as the ``feasibility``'s ``model_params``) the call runs the bank's
+        kernels with one model (:class:`ClosedLoopBank`), whose trajectories are this loop's bit for bit."""
+        if plant_params is None:
+            plant_params = self.plant_params
+        if plant_params is not None or (feasibility is not None and feasibility.model_params is not None):
+            if x0.dim() != 2 or ref.dim() != 2:
+                raise ValueError(f"x0 must be (B,5) and ref (B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
+            if plant_params is not None and _press_shape(plant_params) not in ((28,), (x0.shape[0], 28)):
+                raise ValueError(f"plant_params must be a PressParams, (28,) or (B,28) with B = {x0.shape[0]}, got shape "
+                                 f"{_press_shape(plant_params)}")
+            one = ClosedLoopBank.of_loop(self)
+            r = one.run(x0, ref, process_noise, meas_noise, feasibility, plant_params=plant_params)
+            if feasibility is None:
+                return r["x"][0], r["u"][0]
+            return r["x"][0], r["u"][0], {"u_nn": r["u_nn"][0], "flag": r["flag"][0]}
         dev = x0.device
         if dev.type != "cuda" or ref.device != dev:
             raise RuntimeError(f"ClosedLoop runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
@@ -184,7 +221,7 @@ class ClosedLoop:
 
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
              process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
-             lstm_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None):
+             lstm_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, plant_params=None):
         """``NeuralNetwork.loop``'s two tracks for B trajectories (Functions.py:1116-1273) in two launches: the press
         under the controller (:meth:`run`) and the LSTM surrogate free-running beside it on its own predictions and
         the press's commands (``inference.simulate_rollout`` on that run's ``u``).
@@ -195,8 +232,9 @@ class ClosedLoop:
         reference's (:1266-1273): ``results`` y, y_dot, p1, p2, z (B,T+1) and ref, u (B,T); ``results_LSTM`` y_dot,
         p1, p2, z (B,T+1), row 0 = x0[:,1:5]. With ``feasibility`` (:meth:`run`) ``results['u']`` holds the projected
         commands, which also drive the surrogate's track (Functions.py:1196), and ``results`` gains ``u_nn`` and
-        ``feas_flag`` (B,T)."""
-        x, u, *info = self.run(x0, ref, process_noise, meas_noise, feasibility)
+        ``feas_flag`` (B,T). ``plant_params`` (:meth:`run`) is the press's own; the surrogate was trained on the reference's
+        press and its track is what it was."""
+        x, u, *info = self.run(x0, ref, process_noise, meas_noise, feasibility, plant_params=plant_params)
         s_in, s_out = _model_scales(model_scalers)
         results = {"y": x[:, :, 0], "y_dot": x[:, :, 1], "p1": x[:, :, 2], "p2": x[:, :, 3], "z": x[:, :, 4],
                    "ref": ref.to(torch.float64), "u": u}
@@ -205,6 +243,11 @@ class ClosedLoop:
         track = _shadow_track(x[:, 0, 1:5], u, simulator, s_in, s_out, lstm_noise)
         results_lstm = {"y_dot": track[:, :, 0], "p1": track[:, :, 1], "p2": track[:, :, 2], "z": track[:, :, 3]}
         return results, results_lstm
+
+
+def _press_shape(params) -> tuple:
+    """The shape of ``plant_params`` (a PressParams is one row), without moving or converting it."""
+    return (28,) if isinstance(params, PressParams) else tuple(np.shape(params))
 
 
 def _model_scales(model_scalers: dict):
@@ -268,6 +311,14 @@ class ClosedLoopBank:
         self.out_scale = float(_scale(scalers["output"])[0])
         self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
+    @classmethod
+    def of_loop(cls, loop: "ClosedLoop") -> "ClosedLoopBank":
+        """The bank of ONE model that runs ``loop``'s controller with its scales and step (built through ``__init__``)."""
+        w_inp, b_inp, w_out = (p.detach() for p in _controller_params(loop.controller))
+        bank = types.SimpleNamespace(w_inp=w_inp[None], b_inp=b_inp[None], w_out=w_out.reshape(1, -1))
+        scalers = {"input": np.array(loop.in_scale), "y_dot": loop.ref_scale, "output": loop.out_scale}
+        return cls(bank, scalers, loop.ts, loop.substeps, loop.smooth)
+
     @staticmethod
     def _per_model(name, t, M, tail):
         """Whether ``t`` is ``(M,) + tail`` (True) or ``tail``, one copy shared by all models (False)."""
@@ -279,16 +330,26 @@ class ClosedLoopBank:
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
             meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
-            p_bounds=None):
+            p_bounds=None, plant_params=None):
         """``x0 (B,5)`` or ``(M,B,5)``, ``ref (B,T)`` or ``(M,B,T)``, each noise ``(B,T,5)`` or ``(M,B,T,5)``: without
         the leading M one copy is shared by all models (and read once from memory, not expanded). ``p_bounds``:
         ``((p1_lo, p1_hi), (p2_lo, p2_hi))`` in Pa for the violation statistics; default the ``feasibility``'s own
         bounds, otherwise 0 and 32e6. ``store=False`` skips every per-step store; the statistics, ``x_final`` and
-        ``metrics`` are the storing run's bit for bit."""
+        ``metrics`` are the storing run's bit for bit.
+
+        ``plant_params``: the press each trajectory's loop steps (the TRUE plant) — a :class:`~.plant.PressParams` or a
+        ``(28,)`` row for all, a ``(B,28)`` table shared by the models, or ``(M,B,28)``; shared layouts are read as they
+        lie, through zero strides, not expanded. The projection of ``feasibility`` integrates that object's
+        ``model_params`` (default: the reference's press), one set for the launch — plant and model need not agree, which
+        is what the violation statistics then measure. ``None`` (and no ``model_params``) is the call as it always was:
+        ``fcr_closed_loop_run_bank`` and its kernels; otherwise ``fcr_closed_loop_run_bank_press``."""
         M = self.bank.w_inp.shape[0]
         if x0.dim() not in (2, 3) or x0.shape[-1] != 5 or ref.dim() not in (2, 3):
             raise ValueError(f"x0 must be (B,5) or (M,B,5) and ref (B,T) or (M,B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
         B, T = x0.shape[-2], ref.shape[-1]
+        if plant_params is not None and _press_shape(plant_params) not in ((28,), (B, 28), (M, B, 28)):
+            raise ValueError(f"plant_params must be a PressParams, (28,), (B,28) = {(B, 28)} or (M,B,28) = {(M, B, 28)}, "
+                             f"got shape {_press_shape(plant_params)}")
         stacked = {"x0": self._per_model("x0", x0, M, (B, 5)), "ref": self._per_model("ref", ref, M, (B, T))}
         for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
             stacked[name] = n is not None and self._per_model(name, n, M, (B, T, 5))
@@ -317,6 +378,10 @@ class ClosedLoopBank:
         summary = new(M, 10)
         p = lambda t: None if t is None else t.data_ptr()
         stride = lambda name, per: per if stacked[name] else 0
+        model = None if feasibility is None else feasibility.model_params
+        table = None
+        if plant_params is not None or model is not None:
+            table = as_press_table(PressParams() if plant_params is None else plant_params, dev, "plant_params")
         args = _native.FcrClosedLoopBank(
             B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp), p(b_inp), p(W_out), W_inp.shape[1],
             (ctypes.c_double * 2)(*self.in_scale), self.ref_scale, self.out_scale, p(out["x"]), p(out["u"]), p(wc), p(vc),
@@ -324,8 +389,14 @@ class ClosedLoopBank:
             stride("x0", B * 5), stride("ref", B * T), stride("process_noise", B * T * 5), stride("meas_noise", B * T * 5),
             float(p1_lo), float(p1_hi), float(p2_lo), float(p2_hi), p(out["traj_stats"]), p(out["traj_counts"]),
             p(out["x_final"]), p(summary))
-        _native.check(_native.load().fcr_closed_loop_run_bank(
-            ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "fcr_closed_loop_run_bank")
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if table is None:
+            _native.check(_native.load().fcr_closed_loop_run_bank(ctypes.byref(args), stream), "fcr_closed_loop_run_bank")
+        else:
+            m_struct = None if model is None else model.struct()
+            _native.check(_native.load().fcr_closed_loop_run_bank_press(
+                ctypes.byref(args), p(table), B * 28 if table.dim() == 3 else 0, 28 if table.dim() >= 2 else 0,
+                None if m_struct is None else ctypes.byref(m_struct), stream), "fcr_closed_loop_run_bank_press")
         if M == 0 or B == 0:
             summary.zero_()
         out["metrics"] = {k: summary[:, i] for i, k in enumerate(METRIC_KEYS)}
@@ -334,15 +405,16 @@ class ClosedLoopBank:
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
              process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
              lstm_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
-             p_bounds=None):
+             p_bounds=None, plant_params=None):
         """:meth:`ClosedLoop.loop` for every model: ``(results, results_LSTM)`` keyed as there, every tensor with a
         leading model dimension (``ref`` expanded to ``(M,B,T)``), plus ``results['metrics']``. The surrogate is shared
         by the models, so its track is ONE ``simulate_rollout`` launch on the ``(M*B)`` stack of rows. ``lstm_noise``:
-        ``(B,T,4)`` shared or ``(M,B,T,4)``. The tracks are built from the stored trajectories: ``store`` must be True."""
+        ``(B,T,4)`` shared or ``(M,B,T,4)``. The tracks are built from the stored trajectories: ``store`` must be True.
+        ``plant_params`` (:meth:`run`) is the press's own; the surrogate's track is unaffected by it."""
         if not store:
             raise ValueError("ClosedLoopBank.loop builds both tracks from the stored trajectories: store=True is required")
         s_in, s_out = _model_scales(model_scalers)
-        r = self.run(x0, ref, process_noise, meas_noise, feasibility, True, p_bounds)
+        r = self.run(x0, ref, process_noise, meas_noise, feasibility, store=True, p_bounds=p_bounds, plant_params=plant_params)
         x, u = r["x"], r["u"]
         M, B, T = u.shape
         results = {"y": x[..., 0], "y_dot": x[..., 1], "p1": x[..., 2], "p2": x[..., 3], "z": x[..., 4],

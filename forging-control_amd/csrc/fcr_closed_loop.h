@@ -76,6 +76,7 @@ struct SingleModel {
     __device__ __forceinline__ size_t ref() const { return 0; }
     __device__ __forceinline__ size_t w() const { return 0; }
     __device__ __forceinline__ size_t v() const { return 0; }
+    __device__ __forceinline__ plant::Nominal press(int) const { return {}; }
 };
 
 struct BankStrides {
@@ -96,6 +97,24 @@ struct BankModel {
     __device__ __forceinline__ size_t ref() const { return (size_t)m * s.ref; }
     __device__ __forceinline__ size_t w() const { return (size_t)m * s.w; }
     __device__ __forceinline__ size_t v() const { return (size_t)m * s.v; }
+    __device__ __forceinline__ plant::Nominal press(int) const { return {}; }
+};
+
+// Whose press a lane steps: the models above step the reference's, compile-time constants
+// (plant::Nominal), as they always did. BankPressModel: lane b's own — row m * stride_model + b * stride_traj (elements;
+// 0 = shared, as for x0 / ref / w / v) of a table of plant::kPressFields doubles per row, from which the lane derives its
+// coefficients once, before the loop, into registers.
+struct PressTable {
+    const double *press;
+    long long stride_model, stride_traj;
+};
+
+struct BankPressModel : BankModel {
+    PressTable t;
+    __device__ __forceinline__ BankPressModel(int B, BankStrides st, PressTable table) : BankModel(B, st), t(table) {}
+    __device__ __forceinline__ plant::LaneParams press(int b) const {
+        return plant::derive(t.press + (size_t)m * t.stride_model + (size_t)b * t.stride_traj);
+    }
 };
 
 // max that keeps a NaN once it has one (np.maximum)
@@ -181,6 +200,7 @@ __device__ __forceinline__ void loop_body(ClArgs a, const double *wn, const doub
     __syncthreads();
     const int b = model.block() * kClBlock + threadIdx.x;
     if (b >= a.B) return;
+    const auto pp = model.press(b);                // this lane's press
     const size_t g = (size_t)model.model() * a.B + b;   // the row of the (model-major) outputs
     constexpr bool store = Stats::kStore;
     double x[5], m[5];                            // the press's state; the record the controller and the policy read
@@ -222,7 +242,7 @@ __device__ __forceinline__ void loop_body(ClArgs a, const double *wn, const doub
                 for (int i = 0; i < 5; ++i) vt[i] = vn[model.v() + nt + i];
             }
         }
-        plant::rk4_step<SMOOTH, NOISE>(x, u, a.dt, a.substeps, wt);
+        plant::rk4_step<SMOOTH, NOISE>(x, u, a.dt, a.substeps, wt, pp);
         o += 5;
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
@@ -251,6 +271,14 @@ template <bool SMOOTH, bool NOISE, bool STORE>
 __global__ __launch_bounds__(kClBlock) void closed_loop_bank_kernel(ClArgs a, BankStrides strides, StatsArgs stats,
                                                                     const double *wn, const double *vn) {
     loop_body<SMOOTH, NOISE>(a, wn, vn, PlainCommand{a.u}, BankModel(a.B, strides), LaneStats<STORE>(stats));
+}
+
+// closed_loop_bank_kernel where every trajectory has its own press (fcr_closed_loop_run_bank_press).
+template <bool SMOOTH, bool NOISE, bool STORE>
+__global__ __launch_bounds__(kClBlock) void closed_loop_bank_press_kernel(ClArgs a, BankStrides strides, StatsArgs stats,
+                                                                          const double *wn, const double *vn,
+                                                                          PressTable press) {
+    loop_body<SMOOTH, NOISE>(a, wn, vn, PlainCommand{a.u}, BankPressModel(a.B, strides, press), LaneStats<STORE>(stats));
 }
 
 // The per-model summary of a bank run from its per-trajectory statistics: one block per model, every sum taken in a

@@ -49,14 +49,16 @@ __device__ __forceinline__ double clip(double c, double lo, double hi) { return 
 // max that keeps a NaN once it has one (np.maximum), so a NaN pressure makes v NaN and v <= 0 false
 __device__ __forceinline__ double nan_max(double v, double t) { return (t > v || t != t) ? t : v; }
 
-__device__ __forceinline__ double violation(const double (&x)[5], double u, const FeasArgs &f) {
+// P: the press the projection's model integrates (plant::Nominal, or plant::UniformParams: one set per launch)
+template <class P = plant::Nominal>
+__device__ __forceinline__ double violation(const double (&x)[5], double u, const FeasArgs &f, P p = {}) {
     double xs[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) xs[i] = x[i];
     double v = -HUGE_VAL;
 #pragma unroll 1
     for (int s = 0; s < 2; ++s) {
-        plant::rk4_step<false>(xs, u, f.dt, f.substeps);
+        plant::rk4_step<false, false>(xs, u, f.dt, f.substeps, nullptr, p);
         const double p1 = xs[2] * kPScale, p2 = xs[3] * kPScale;
         v = nan_max(v, nan_max(f.lo1 - p1, p1 - f.hi1));
         v = nan_max(v, nan_max(f.lo2 - p2, p2 - f.hi2));
@@ -64,7 +66,8 @@ __device__ __forceinline__ double violation(const double (&x)[5], double u, cons
     return v;
 }
 
-__device__ __forceinline__ Projected project(const double (&x)[5], double u_nn, const FeasArgs &f) {
+template <class P = plant::Nominal>
+__device__ __forceinline__ Projected project(const double (&x)[5], double u_nn, const FeasArgs &f, P p = {}) {
     const double delta = (f.u_hi - f.u_lo) / (double)(1 << f.expand);
     const int n_probe = 2 * (f.expand + 1), n_it = 1 + n_probe + f.bisect;
     double a = u_nn, g = u_nn, vg = 0.0;        // the bracket: a infeasible, g feasible (once found)
@@ -85,7 +88,7 @@ __device__ __forceinline__ Projected project(const double (&x)[5], double u_nn, 
         }
         const bool active = it == 0 || (probing ? need && !found : found);
         if (active) {
-            const double vc = violation(x, c, f);
+            const double vc = violation(x, c, f, p);
             const bool ok = vc <= 0.0;
             if (it == 0) {
                 v0 = vc;
@@ -143,16 +146,37 @@ __global__ __launch_bounds__(kFeasBlock) void feasibility_project_kernel(FeasArg
     if (v) v[b] = r.v;
 }
 
+// feasibility_project_kernel on a model press other than the reference's: its coefficients by value, in scalar registers.
+__global__ __launch_bounds__(kFeasBlock) void feasibility_project_press_kernel(FeasArgs f, plant::UniformParams p, int B,
+                                                                               const double *__restrict__ x,
+                                                                               const double *__restrict__ u_nn,
+                                                                               double *__restrict__ u,
+                                                                               int32_t *__restrict__ flag,
+                                                                               double *__restrict__ v) {
+    const int b = blockIdx.x * kFeasBlock + threadIdx.x;
+    if (b >= B) return;
+    double xs[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) xs[i] = x[(size_t)b * 5 + i];
+    const Projected r = project(xs, u_nn[b], f, p);
+    u[b] = r.u;
+    flag[b] = r.flag;
+    if (v) v[b] = r.v;
+}
+
 // The command policy of the loop with recovery (closed_loop::loop_body): the projection of the controller's command
 // from the record the controller read, between the controller and the press. Stores u_nn, u and flag. The projection's
-// own model has no noise, is always the non-smooth one and has its own step (FeasArgs).
+// own model has no noise, is always the non-smooth one, has its own step (FeasArgs) and its own press P — the model's,
+// which need not be the press the loop steps.
+template <class P = plant::Nominal>
 struct ProjectedCommand {
     FeasArgs f;
     double *u, *u_nn;
     int32_t *flag;
-    __device__ __forceinline__ ProjectedCommand row(size_t r) const { return {f, u + r, u_nn + r, flag + r}; }
+    P p;
+    __device__ __forceinline__ ProjectedCommand row(size_t r) const { return {f, u + r, u_nn + r, flag + r, p}; }
     __device__ __forceinline__ double operator()(const double (&m)[5], double un, int t) const {
-        const Projected r = project(m, un, f);
+        const Projected r = project(m, un, f, p);
         u_nn[t] = un;
         u[t] = r.u;
         flag[t] = r.flag;
@@ -160,7 +184,7 @@ struct ProjectedCommand {
     }
     // as called under closed_loop::LaneStats: the stores are optional, the flag goes to the lane's counts
     __device__ __forceinline__ double operator()(const double (&m)[5], double un, int t, bool store, int &fl) const {
-        const Projected r = project(m, un, f);
+        const Projected r = project(m, un, f, p);
         if (store) {
             u_nn[t] = un;
             u[t] = r.u;
@@ -175,7 +199,7 @@ template <bool SMOOTH, bool NOISE>
 __global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_recover_kernel(closed_loop::ClArgs a, FeasArgs f,
                                                                                     const double *wn, const double *vn,
                                                                                     double *u_nn, int32_t *flag) {
-    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand{f, a.u, u_nn, flag});
+    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand<>{f, a.u, u_nn, flag});
 }
 
 // closed_loop_bank_kernel with recovery: u_nn and flag are model-major like a.u, and null with it.
@@ -183,8 +207,17 @@ template <bool SMOOTH, bool NOISE, bool STORE>
 __global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_bank_recover_kernel(
     closed_loop::ClArgs a, FeasArgs f, closed_loop::BankStrides strides, closed_loop::StatsArgs stats, const double *wn,
     const double *vn, double *u_nn, int32_t *flag) {
-    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand{f, a.u, u_nn, flag},
+    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand<>{f, a.u, u_nn, flag},
                                           closed_loop::BankModel(a.B, strides), closed_loop::LaneStats<STORE>(stats));
+}
+
+// closed_loop_bank_recover_kernel where every trajectory has its own press and the projection integrates `model`.
+template <bool SMOOTH, bool NOISE, bool STORE>
+__global__ __launch_bounds__(closed_loop::kClBlock) void closed_loop_bank_recover_press_kernel(
+    closed_loop::ClArgs a, FeasArgs f, closed_loop::BankStrides strides, closed_loop::StatsArgs stats, const double *wn,
+    const double *vn, double *u_nn, int32_t *flag, closed_loop::PressTable press, plant::UniformParams model) {
+    closed_loop::loop_body<SMOOTH, NOISE>(a, wn, vn, ProjectedCommand<plant::UniformParams>{f, a.u, u_nn, flag, model},
+                                          closed_loop::BankPressModel(a.B, strides, press), closed_loop::LaneStats<STORE>(stats));
 }
 
 }  // namespace feasibility

@@ -37,9 +37,80 @@ int feasibility_args(const char *who, const fcr_feasibility *f, feasibility::Fea
     return FCR_OK;
 }
 
+static_assert(sizeof(fcr_press) == plant::kPressFields * sizeof(double), "fcr_press is one row of a parameter table");
+
+// a host-side press (the model a projection integrates) -> its coefficients, or a message
+int press_model(const char *who, const fcr_press *model, plant::UniformParams *out) {
+    fcr_press nominal;
+    fcr_press_nominal(&nominal);
+    const double *row = (const double *)(model ? model : &nominal);
+    static const char *const names[plant::kPressFields] = {
+        "m_mass", "b_damp", "ft", "d1", "d2", "g", "kb", "v1_0", "v2_0", "kl_1", "kl_2", "cd", "rho", "d",
+        "ps", "pt", "mu", "k", "w0", "h0", "b0", "t_def", "t1", "m0", "m1", "m2", "m3", "m4"};
+    static const int positive[] = {0, 3, 4, 7, 8, 12, 18, 19, 20, 22};   // divided by, or under a root
+    for (int i = 0; i < plant::kPressFields; ++i)
+        if (!(row[i] - row[i] == 0.0)) return fail(FCR_EINVAL, "%s: model field %s=%g is not finite", who, names[i], row[i]);
+    for (const int i : positive)
+        if (!(row[i] > 0.0)) return fail(FCR_EINVAL, "%s: model field %s=%g must be positive", who, names[i], row[i]);
+    *out = plant::derive(row);
+    return FCR_OK;
+}
+
+// a parameter table's pointer, checked once the call is known not to be empty (B = 0 reads no row), or a message
+int press_pointer(const char *who, const double *press) {
+    if (!press) return fail(FCR_EINVAL, "%s: the parameter table is NULL", who);
+    if (((uintptr_t)press) & 7) return fail(FCR_EINVAL, "%s: the parameter table must be 8-byte aligned (fp64)", who);
+    return FCR_OK;
+}
+
+// a parameter table's strides (include/fcr.h), or a message
+int press_strides(const char *who, long long stride_model, long long stride_traj, int B) {
+    if (stride_model < 0 || stride_traj < 0)
+        return fail(FCR_EINVAL, "%s: a parameter stride is negative (model %lld, trajectory %lld)", who, stride_model, stride_traj);
+    if (stride_traj % plant::kPressFields)
+        return fail(FCR_EINVAL, "%s: stride_traj=%lld must be 0 (shared) or a multiple of %d", who, stride_traj, plant::kPressFields);
+    if (stride_model && (stride_model % plant::kPressFields || stride_model < (long long)B * stride_traj))
+        return fail(FCR_EINVAL, "%s: stride_model=%lld must be 0 (shared) or a multiple of %d that is >= B * stride_traj = %lld",
+                    who, stride_model, plant::kPressFields, (long long)B * stride_traj);
+    return FCR_OK;
+}
+
+// fcr_closed_loop_run_bank (table = null: the reference's press, the kernels without parameters) and
+// fcr_closed_loop_run_bank_press (table, model: checked by the caller)
+int run_bank(const char *who, const fcr_closed_loop_bank *c, const closed_loop::PressTable *table,
+             const plant::UniformParams *model, void *stream);
+
 }  // namespace
 
 extern "C" {
+
+void fcr_press_nominal(fcr_press *out) {
+    if (!out) return;
+    *out = fcr_press{plant::M_MASS, plant::B_DAMP, plant::FT, plant::D1, plant::D2, plant::G, plant::KB, plant::V1_0,
+                     plant::V2_0, plant::KL_1, plant::KL_2, plant::CD, plant::RHO, plant::D, plant::PS, plant::PT,
+                     plant::MU, plant::K, plant::W0, plant::H0, plant::B0, plant::T_DEF, plant::T1, plant::M0,
+                     plant::M1, plant::M2, plant::M3, plant::M4};
+}
+
+int fcr_plant_rk4_press(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x0,
+                        const double *u, double *x, const double *press, int64_t stride_traj, void *stream) {
+    const char *who = "fcr_plant_rk4_press";
+    if (B < 0 || S < 0) return fail(FCR_EINVAL, "%s: B=%d, S=%d must be >= 0", who, B, S);
+    if (const int rc = check_step(who, "", ts, substeps)) return rc;
+    if (smooth != 0 && smooth != 1) return fail(FCR_EINVAL, "%s: smooth=%d must be 0 or 1", who, smooth);
+    if ((long long)B * (S + 1) * 5 > (1LL << 40)) return fail(FCR_EINVAL, "%s: B*(S+1) too large", who);
+    if (const int rc = press_strides(who, 0, stride_traj, B)) return rc;
+    if (B == 0) return FCR_OK;
+    if (const int rc = press_pointer(who, press)) return rc;
+    if (!x0 || !x || (S > 0 && !u)) return fail(FCR_EINVAL, "%s: a required pointer is NULL", who);
+    if ((((uintptr_t)x0) | ((uintptr_t)u) | ((uintptr_t)x)) & 7)
+        return fail(FCR_EINVAL, "%s: buffers must be 8-byte aligned (fp64)", who);
+    const dim3 grid((B + plant::kPlantBlock - 1) / plant::kPlantBlock);
+    hipLaunchKernelGGL(smooth ? plant::plant_rk4_press_kernel<true> : plant::plant_rk4_press_kernel<false>, grid,
+                       dim3(plant::kPlantBlock), 0, (hipStream_t)stream, B, S, ts / substeps, substeps, x0, u, x, press,
+                       (long long)stride_traj);
+    return launch_check("plant_rk4_press_kernel");
+}
 
 int fcr_plant_rk4(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x0,
                   const double *u, double *x, void *stream) {
@@ -135,7 +206,45 @@ int fcr_closed_loop_run(const fcr_closed_loop *c, void *stream) {
 }
 
 int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *c, void *stream) {
-    const char *who = "fcr_closed_loop_run_bank";
+    return run_bank("fcr_closed_loop_run_bank", c, nullptr, nullptr, stream);
+}
+
+int fcr_closed_loop_run_bank_press(const fcr_closed_loop_bank *c, const double *press, int64_t stride_model,
+                                   int64_t stride_traj, const fcr_press *model, void *stream) {
+    const char *who = "fcr_closed_loop_run_bank_press";
+    if (!c) return fail(FCR_EINVAL, "%s: args is NULL", who);
+    if (const int rc = press_strides(who, stride_model, stride_traj, c->B)) return rc;
+    plant::UniformParams mp;
+    if (const int rc = press_model(who, model, &mp)) return rc;
+    const closed_loop::PressTable table{press, (long long)stride_model, (long long)stride_traj};
+    return run_bank(who, c, &table, &mp, stream);
+}
+
+int fcr_feasibility_project_press(const fcr_feasibility *f, const fcr_press *model, int32_t B, const double *x,
+                                  const double *u_nn, double *u, int32_t *flag, double *v, void *stream) {
+    const char *who = "fcr_feasibility_project_press";
+    if (!f) return fail(FCR_EINVAL, "%s: parameters is NULL", who);
+    if (B < 0) return fail(FCR_EINVAL, "%s: B=%d must be >= 0", who, B);
+    feasibility::FeasArgs fa{};
+    if (const int rc = feasibility_args(who, f, &fa)) return rc;
+    plant::UniformParams mp;
+    if (const int rc = press_model(who, model, &mp)) return rc;
+    if (B == 0) return FCR_OK;
+    if (!x || !u_nn || !u || !flag) return fail(FCR_EINVAL, "%s: a required pointer is NULL", who);
+    if (((((uintptr_t)x) | ((uintptr_t)u_nn) | ((uintptr_t)u) | ((uintptr_t)v)) & 7) || (((uintptr_t)flag) & 3))
+        return fail(FCR_EINVAL, "%s: fp64 buffers must be 8-byte and flag 4-byte aligned", who);
+    hipLaunchKernelGGL(feasibility::feasibility_project_press_kernel,
+                       dim3((B + feasibility::kFeasBlock - 1) / feasibility::kFeasBlock), dim3(feasibility::kFeasBlock), 0,
+                       (hipStream_t)stream, fa, mp, B, x, u_nn, u, flag, v);
+    return launch_check("feasibility_project_press_kernel");
+}
+
+}  // extern "C"
+
+namespace {
+
+int run_bank(const char *who, const fcr_closed_loop_bank *c, const closed_loop::PressTable *table,
+             const plant::UniformParams *model, void *stream) {
     if (!c) return fail(FCR_EINVAL, "%s: args is NULL", who);
     if (c->n_models < 0) return fail(FCR_EINVAL, "%s: n_models=%d must be >= 0", who, c->n_models);
     if (c->B < 0 || c->T < 0) return fail(FCR_EINVAL, "%s: B=%d, T=%d must be >= 0", who, c->B, c->T);
@@ -157,6 +266,8 @@ int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *c, void *stream) {
     if (c->n_models * bpm > INT32_MAX || (long long)c->n_models * c->B * ((long long)c->T + 1) * 5 > (1LL << 40))
         return fail(FCR_EINVAL, "%s: n_models*B*(T+1) too large", who);
     if (c->n_models == 0 || c->B == 0) return FCR_OK;
+    if (table)
+        if (const int rc = press_pointer(who, table->press)) return rc;
     if (!c->x0 || !c->ctrl_w_inp || !c->ctrl_b_inp || !c->ctrl_w_out || !c->traj_stats || !c->traj_counts || !c->x_final ||
         !c->summary || (c->T > 0 && !c->ref))
         return fail(FCR_EINVAL, "%s: a required pointer is NULL", who);
@@ -180,7 +291,24 @@ int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *c, void *stream) {
     const dim3 grid((unsigned)(c->n_models * bpm)), block(closed_loop::kClBlock);
     // the single-model call's choice of instantiation; T = 0 copies x0 and writes zero statistics
     const bool sm = c->smooth, noise = c->T > 0 && (c->process_noise || c->meas_noise), store = c->x != nullptr;
-    if (recover) {
+    if (table && recover) {
+        using feasibility::closed_loop_bank_recover_press_kernel;
+        static constexpr decltype(&closed_loop_bank_recover_press_kernel<false, false, false>) k[2][2][2] = {
+            {{closed_loop_bank_recover_press_kernel<false, false, false>, closed_loop_bank_recover_press_kernel<false, false, true>},
+             {closed_loop_bank_recover_press_kernel<false, true, false>, closed_loop_bank_recover_press_kernel<false, true, true>}},
+            {{closed_loop_bank_recover_press_kernel<true, false, false>, closed_loop_bank_recover_press_kernel<true, false, true>},
+             {closed_loop_bank_recover_press_kernel<true, true, false>, closed_loop_bank_recover_press_kernel<true, true, true>}}};
+        hipLaunchKernelGGL(k[sm][noise][store], grid, block, 0, s, a, fa, st, sa, c->process_noise, c->meas_noise, c->u_nn,
+                           c->feas_flag, *table, *model);
+    } else if (table) {
+        using closed_loop::closed_loop_bank_press_kernel;
+        static constexpr decltype(&closed_loop_bank_press_kernel<false, false, false>) k[2][2][2] = {
+            {{closed_loop_bank_press_kernel<false, false, false>, closed_loop_bank_press_kernel<false, false, true>},
+             {closed_loop_bank_press_kernel<false, true, false>, closed_loop_bank_press_kernel<false, true, true>}},
+            {{closed_loop_bank_press_kernel<true, false, false>, closed_loop_bank_press_kernel<true, false, true>},
+             {closed_loop_bank_press_kernel<true, true, false>, closed_loop_bank_press_kernel<true, true, true>}}};
+        hipLaunchKernelGGL(k[sm][noise][store], grid, block, 0, s, a, st, sa, c->process_noise, c->meas_noise, *table);
+    } else if (recover) {
         using feasibility::closed_loop_bank_recover_kernel;
         static constexpr decltype(&closed_loop_bank_recover_kernel<false, false, false>) k[2][2][2] = {
             {{closed_loop_bank_recover_kernel<false, false, false>, closed_loop_bank_recover_kernel<false, false, true>},
@@ -198,11 +326,17 @@ int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *c, void *stream) {
              {closed_loop_bank_kernel<true, true, false>, closed_loop_bank_kernel<true, true, true>}}};
         hipLaunchKernelGGL(k[sm][noise][store], grid, block, 0, s, a, st, sa, c->process_noise, c->meas_noise);
     }
-    if (const int rc = launch_check(recover ? "closed_loop_bank_recover_kernel" : "closed_loop_bank_kernel")) return rc;
+    if (const int rc = launch_check(table ? (recover ? "closed_loop_bank_recover_press_kernel" : "closed_loop_bank_press_kernel")
+                                          : (recover ? "closed_loop_bank_recover_kernel" : "closed_loop_bank_kernel")))
+        return rc;
     const closed_loop::RedArgs ra{c->B, c->T, c->ref_stride, c->ref, c->traj_stats, c->traj_counts, c->summary};
     hipLaunchKernelGGL(closed_loop::loop_stats_reduce_kernel, dim3(c->n_models), dim3(closed_loop::kRedBlock), 0, s, ra);
     return launch_check("loop_stats_reduce_kernel");
 }
+
+}  // namespace
+
+extern "C" {
 
 int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,
                             int32_t *flag, double *v, void *stream) {

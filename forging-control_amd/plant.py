@@ -10,7 +10,9 @@ trajectory through S commands with its state kept in registers.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
+import numpy as np
 import torch
 
 from . import _native
@@ -20,13 +22,117 @@ TS_REFERENCE = 0.001                              # template_mpc.py:23 (controll
 SUBSTEPS_REFERENCE = 4                            # Functions.py:1760
 
 
+@dataclasses.dataclass(frozen=True)
+class PressParams:
+    """The 28 physical constants of ``forging_model`` / ``template_model`` under the reference's names
+    (Functions.py:1636-1695); the defaults are the reference's values, the ones every call without parameters is
+    compiled with. One set is one row of a parameter table: 28 fp64 values in the order of :attr:`NAMES`
+    (``fcr_press``, include/fcr.h). The friction knee (0.5 m/s) and the smooth model's epsilon belong to the model's form
+    and are not parameters."""
+    M_MASS: float = 90000.0
+    B_DAMP: float = 25000.0
+    FT: float = 200000.0
+    D1: float = 0.6
+    D2: float = 0.5
+    G: float = 9.81
+    KB: float = 22e9
+    V1_0: float = 0.3
+    V2_0: float = 0.1
+    KL_1: float = 8e-13
+    KL_2: float = 14e-14
+    CD: float = 0.63
+    RHO: float = 858.0
+    D: float = 0.006
+    PS: float = 32e6
+    PT: float = 101325.0
+    MU: float = 0.3
+    K: float = 1.115
+    W0: float = 0.2
+    H0: float = 0.5
+    B0: float = 0.1
+    T_DEF: float = 900.0
+    T1: float = 0.005
+    M0: float = 1200e6
+    M1: float = -0.0025
+    M2: float = -0.0587
+    M3: float = 0.1165
+    M4: float = -0.0065
+
+    NAMES = ("M_MASS", "B_DAMP", "FT", "D1", "D2", "G", "KB", "V1_0", "V2_0", "KL_1", "KL_2", "CD", "RHO", "D", "PS", "PT",
+             "MU", "K", "W0", "H0", "B0", "T_DEF", "T1", "M0", "M1", "M2", "M3", "M4")
+    # the equations divide by these or take their root: they must be positive
+    POSITIVE = ("M_MASS", "D1", "D2", "V1_0", "V2_0", "RHO", "W0", "H0", "B0", "T1")
+
+    def replace(self, **kw) -> "PressParams":
+        """A copy with the named fields changed."""
+        return dataclasses.replace(self, **kw)
+
+    def as_row(self) -> np.ndarray:
+        """``(28,)`` fp64, the fields in the order of :attr:`NAMES`."""
+        return np.array([getattr(self, n) for n in self.NAMES], dtype=np.float64)
+
+    def struct(self) -> _native.FcrPress:
+        return _native.FcrPress(*self.as_row())
+
+    def table(self, n: int, device=None) -> torch.Tensor:
+        """``(n, 28)`` fp64: this set for each of ``n`` trajectories."""
+        return torch.tensor(np.tile(self.as_row(), (int(n), 1)), dtype=torch.float64, device=device)
+
+    def sample(self, n: int, rel: dict, dist: str = "uniform", rng: np.random.RandomState | None = None,
+               device=None) -> torch.Tensor:
+        """``(n, 28)`` fp64: ``n`` presses around this one. ``rel`` maps a field name to a relative half-width
+        (``dist="uniform"``: the field is this set's value times ``1 + U(-rel, rel)``) or a relative standard
+        deviation (``"normal"``: times ``1 + rel * N(0, 1)``); fields ``rel`` does not name keep this set's value.
+
+        Draw order (fixed): the named fields in the order of :attr:`NAMES` — not of ``rel`` — each as ONE call of
+        ``rng.uniform(-1, 1, n)`` or ``rng.standard_normal(n)``. ``rng`` defaults to ``RandomState(0)``."""
+        unknown = sorted(set(rel) - set(self.NAMES))
+        if unknown:
+            raise ValueError(f"PressParams.sample: unknown fields {unknown}; the fields are {self.NAMES}")
+        if dist not in ("uniform", "normal"):
+            raise ValueError(f"PressParams.sample: dist must be 'uniform' or 'normal', got {dist!r}")
+        rng = np.random.RandomState(0) if rng is None else rng
+        out = np.tile(self.as_row(), (int(n), 1))
+        for i, name in enumerate(self.NAMES):
+            if name in rel:
+                z = rng.uniform(-1.0, 1.0, int(n)) if dist == "uniform" else rng.standard_normal(int(n))
+                out[:, i] *= 1.0 + float(rel[name]) * z
+        return torch.tensor(out, dtype=torch.float64, device=device)
+
+    @classmethod
+    def validate(cls, table: torch.Tensor) -> bool:
+        """Whether every row of ``table (..., 28)`` is a press the equations can integrate: all fields finite and
+        :attr:`POSITIVE`'s positive. One reduction (and one host read of its result); the kernels do not check."""
+        if table.shape[-1] != len(cls.NAMES):
+            raise ValueError(f"a parameter table has {len(cls.NAMES)} columns, got shape {tuple(table.shape)}")
+        pos = torch.zeros(len(cls.NAMES), dtype=torch.bool, device=table.device)
+        pos[[cls.NAMES.index(n) for n in cls.POSITIVE]] = True
+        return bool((torch.isfinite(table) & ((table > 0) | ~pos)).all().item())
+
+
+def as_press_table(params, device, what: str = "params") -> torch.Tensor:
+    """``params`` (a :class:`PressParams`, or an array / tensor whose last dimension is 28) as a contiguous fp64 tensor
+    on ``device``; an array's shape is kept."""
+    if isinstance(params, PressParams):
+        return torch.tensor(params.as_row(), dtype=torch.float64, device=device)
+    t = torch.as_tensor(params)
+    if t.dim() < 1 or t.shape[-1] != len(PressParams.NAMES):
+        raise ValueError(f"{what}: the last dimension of a parameter table is {len(PressParams.NAMES)}, got {tuple(t.shape)}")
+    if torch.is_tensor(params) and params.device != torch.device(device):
+        raise RuntimeError(f"{what} must be on {device}, found it on {params.device}")
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
 def forging_rk4(x0: torch.Tensor, u: torch.Tensor, ts: float = TS_REFERENCE,
-                substeps: int = SUBSTEPS_REFERENCE, smooth: bool = False) -> torch.Tensor:
+                substeps: int = SUBSTEPS_REFERENCE, smooth: bool = False, params=None) -> torch.Tensor:
     """States of B trajectories under S held commands: x0 (B, 5), u (B, S) -> x (B, S+1, 5), fp64.
 
     ``x[:, 0] = x0`` and ``x[:, t+1] = F(x[:, t], u[:, t])`` with F the reference's RK4 integrator.
     ``smooth=True`` integrates template_model's dynamics (smooth_relu-floored pressures) instead of
-    forging_model's. Runs on a ROCm device only; there is no CPU path."""
+    forging_model's. ``params``: the press — a :class:`PressParams` or a ``(28,)`` row for all trajectories, or a
+    ``(B, 28)`` table, one row per trajectory (``fcr_plant_rk4_press``; a shared row is read through a zero stride, not
+    expanded); ``None`` is the reference's press, the call as it always was. Runs on a ROCm device only; there is no CPU
+    path."""
     if x0.device.type != "cuda" or u.device != x0.device:
         raise RuntimeError(f"forging_rk4 runs on a ROCm device only (got x0 on {x0.device}, u on {u.device})")
     if x0.dim() != 2 or x0.shape[1] != 5:
@@ -40,6 +146,17 @@ def forging_rk4(x0: torch.Tensor, u: torch.Tensor, ts: float = TS_REFERENCE,
     uc = u.to(torch.float64).contiguous()
     out = torch.empty(B, S + 1, 5, dtype=torch.float64, device=x0.device)
     lib = _native.load()
+    if params is not None:
+        tab = as_press_table(params, x0.device)
+        if tuple(tab.shape) not in ((28,), (B, 28)):
+            raise ValueError(f"params must be a PressParams, (28,) or (B, 28) = {(B, 28)}, got {tuple(tab.shape)}")
+        _native.check(lib.fcr_plant_rk4_press(B, S, float(ts), int(substeps), int(bool(smooth)),
+                                              ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
+                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(tab.data_ptr()),
+                                              28 if tab.dim() == 2 else 0,
+                                              ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)),
+                      "fcr_plant_rk4_press")
+        return out
     _native.check(lib.fcr_plant_rk4(B, S, float(ts), int(substeps), int(bool(smooth)),
                                     ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
                                     ctypes.c_void_p(out.data_ptr()),
@@ -54,12 +171,12 @@ class ForgingRK4:
     Mirrors the CasADi Function's call convention (keyword inputs ``x0``, ``u``; output ``xf``) so the
     harness's ``F(x0=x, u=u)['xf']`` reads the same, for a batch of trajectories at once."""
 
-    def __init__(self, TS: float = TS_REFERENCE, substeps: int = SUBSTEPS_REFERENCE, smooth: bool = False):
-        self.TS, self.substeps, self.smooth = float(TS), int(substeps), bool(smooth)
+    def __init__(self, TS: float = TS_REFERENCE, substeps: int = SUBSTEPS_REFERENCE, smooth: bool = False, params=None):
+        self.TS, self.substeps, self.smooth, self.params = float(TS), int(substeps), bool(smooth), params
 
     def __call__(self, x0: torch.Tensor, u: torch.Tensor) -> dict:
-        return {"xf": forging_rk4(x0, u.reshape(-1, 1), self.TS, self.substeps, self.smooth)[:, 1]}
+        return {"xf": forging_rk4(x0, u.reshape(-1, 1), self.TS, self.substeps, self.smooth, self.params)[:, 1]}
 
     def rollout(self, x0: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
         """All S+1 states of the trajectories under commands u (B, S)."""
-        return forging_rk4(x0, u, self.TS, self.substeps, self.smooth)
+        return forging_rk4(x0, u, self.TS, self.substeps, self.smooth, self.params)

@@ -340,6 +340,47 @@ typedef struct fcr_closed_loop_bank {
 int fcr_closed_loop_run_bank(const fcr_closed_loop_bank *args, void *stream);
 
 /*
+ * The press and the workpiece as data (a pure addition to ABI 8). fcr_press holds the 28 physical constants of
+ * forging_model / template_model under the reference's names (Functions.py:1636-1695): moving mass, damping, friction,
+ * plunger diameters, gravity, bulk modulus, chamber volumes, leakages, valve discharge coefficient, oil density, valve
+ * diameter, supply and tank pressure, friction coefficient and K of the deformation resistance, billet width, height
+ * and bite, its temperature, the valve's time constant, and the flow-stress coefficients. fcr_press_nominal writes the
+ * reference's values, the ones every call without parameters is compiled with. The friction knee (0.5 m/s) and the
+ * smooth model's epsilon belong to the model's form and are not parameters.
+ *
+ * A parameter TABLE is device memory, fp64, 8-byte aligned, 28 doubles per row in the order of the struct's fields; a
+ * kernel lane reads ITS trajectory's row once and derives its coefficients from it. Rows are addressed by strides in
+ * ELEMENTS, 0 = shared (as x0_stride etc. above): trajectory b of model m reads row
+ *   press + m * stride_model + b * stride_traj.
+ * B = 0 (or n_models = 0) stays a no-op and reads no row: the table may then be NULL. A stride is 0 or a multiple of 28; stride_model, unless 0, is at least B * stride_traj (and at least 28). Nothing
+ * synchronises inside a call, so the rows themselves are not checked: a bad row propagates NaN, as a bad x0 does.
+ * A host-side `model` (below) IS checked: every field finite, and m_mass, t1, rho, d1, d2, v1_0, v2_0, w0, h0, b0 > 0
+ * (the equations divide by them or take their root).
+ *
+ *   fcr_plant_rk4_press            fcr_plant_rk4 where trajectory b integrates the press of row b * stride_traj.
+ *   fcr_feasibility_project_press  fcr_feasibility_project where the projection integrates `model` (NULL = nominal).
+ *   fcr_closed_loop_run_bank_press fcr_closed_loop_run_bank where the loop steps each trajectory's own press (the TRUE
+ *                                  plant, from the table) and the feasibility projection, if any, integrates `model`
+ *                                  (the controller's idea of the press; NULL = nominal), one set for the launch.
+ * With the nominal row everywhere and the nominal model each computes what its counterpart computes, bit for bit.
+ */
+typedef struct fcr_press {
+    double m_mass, b_damp, ft, d1, d2, g, kb, v1_0, v2_0, kl_1, kl_2, cd, rho, d, ps, pt, mu, k, w0, h0, b0, t_def, t1,
+        m0, m1, m2, m3, m4;
+} fcr_press;
+
+void fcr_press_nominal(fcr_press *out);
+
+int fcr_plant_rk4_press(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x0,
+                        const double *u, double *x, const double *press, int64_t stride_traj, void *stream);
+
+int fcr_feasibility_project_press(const fcr_feasibility *f, const fcr_press *model, int32_t B, const double *x,
+                                  const double *u_nn, double *u, int32_t *flag, double *v, void *stream);
+
+int fcr_closed_loop_run_bank_press(const fcr_closed_loop_bank *args, const double *press, int64_t stride_model,
+                                   int64_t stride_traj, const fcr_press *model, void *stream);
+
+/*
  * Training-sample windows: the tables of the concatenated per-trajectory
  * SequenceDatasets (Functions.py:92-132, built by Data.get_individual_dataset :479-516 and
  * ConcatDataset, UL/Main.py:270-279), resident in device memory.
