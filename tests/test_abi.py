@@ -173,3 +173,40 @@ def test_workspace_size_refuses_overflowing_dims(B, N, H):
     rc = lib.fcr_workspace_size(ctypes.byref(dims(B=B, N=N, H=H)), None, 1, ctypes.byref(out))
     assert rc == -1 and out.value == 0
     assert "too large" in lib.fcr_last_error().decode()
+
+
+def _ws_rc(d, backward=1):
+    lib = fca._native.load()
+    out = ctypes.c_size_t(0)
+    o = fca._native.make_options(wide_keep_budget=0)            # H > 52: no kept windows, whatever the default policy
+    return lib.fcr_workspace_size(ctypes.byref(d), ctypes.byref(o), backward, ctypes.byref(out)), out.value
+
+
+@pytest.mark.parametrize("H", [50, 16, 64])
+def test_ctrl_hidden_is_accepted_up_to_52(H):
+    """check_dims: the 13 x 4 controller slots hold 1..52 units, in every kernel family's workspace query."""
+    for ch in (1, 52):
+        rc, size = _ws_rc(dims(B=64, N=4, H=H, ctrl_hidden=ch))
+        assert rc == 0 and size > 0, (H, ch)
+    for ch in (0, 53):
+        rc, size = _ws_rc(dims(B=64, N=4, H=H, ctrl_hidden=ch))
+        assert rc == -4 and size == 0, (H, ch)                    # FCR_EUNSUPPORTED
+        assert f"ctrl_hidden={ch}" in fca._native.load().fcr_last_error().decode()
+
+
+@pytest.mark.parametrize("H,B,N", [(50, 15, 10), (50, 700, 3), (64, 700, 3)])
+def test_workspace_grows_with_ctrl_hidden_by_the_partial_gradient_slab(H, B, N):
+    """H <= 52: the only slab ctrl_hidden sizes is the partial controller gradients (make_layout's fnn_part): 5 floats
+    (three of g_W_inp, g_b_inp, g_W_out) per unit and per block of 1024 (trajectory, step) items, rounded up to the
+    arena's 256 bytes; the controller itself travels in the fixed 13 x 4 slots. H > 52 (make_wide) lays that slab out
+    with the backward only, and keeps its own copies of W_inp, b_inp and W_out in both."""
+    blocks = (B * N + 1023) // 1024
+    up = lambda n: (n + 255) // 256 * 256
+    copies = (lambda ch: up(4 * ch * 3) + 2 * up(4 * ch)) if H > 52 else (lambda ch: 0)
+    slab = lambda ch: up(4 * blocks * ch * 5)
+    size = lambda ch, bw: _ws_rc(dims(B=B, N=N, H=H, ctrl_hidden=ch), bw)[1]
+    for ch in (1, 2, 13, 50, 51, 52):
+        assert size(ch, 1) - size(1, 1) == slab(ch) - slab(1) + copies(ch) - copies(1), (ch, blocks)
+        fwd = size(ch, 0) - size(1, 0) - (copies(ch) - copies(1))
+        assert fwd == (0 if H > 52 else slab(ch) - slab(1)), (ch, fwd)
+    assert size(52, 1) > size(1, 1)

@@ -317,3 +317,72 @@ def test_closed_loop_loop_returns_both_tracks():
         err = np.abs(got.cpu().numpy() - track[:, :, i]).max() / np.abs(track[:, :, i]).max()
         print(f"results_LSTM[{k}]: {err:.3g}")
         assert err <= 1e-5, (k, err)
+
+
+# ---------------------------------------------------------------------------------------------
+# the single-model closed loop at other controller widths than 50
+# ---------------------------------------------------------------------------------------------
+def _cl_constants():
+    """kClBlock and kClMaxHidden of csrc/fcr_closed_loop.h: the lanes of a block, which also load the controller into
+    LDS (``for i = threadIdx.x; i < hidden; i += kClBlock``), and the widest controller the kernels take."""
+    import re
+    from conftest import ROOT
+    text = open(os.path.join(ROOT, "forging-control_amd", "csrc", "fcr_closed_loop.h")).read()
+    return tuple(int(re.search(rf"constexpr int {k} = (\d+);", text).group(1)) for k in ("kClBlock", "kClMaxHidden"))
+
+
+def loop_widths():
+    """1, the widest, and 65 (past the 64 of the stand-alone FNN kernels; it takes the LDS loader past one pass only if
+    a block has fewer than 65 lanes, else kClBlock + 1 does where the kernels accept it)."""
+    block, widest = _cl_constants()
+    second_pass = 65 if block < 65 else block + 1
+    return sorted({1, 65, widest} | ({second_pass} if second_pass <= widest else set()))
+
+
+def widened_controller(hidden):
+    """The reference's 50-unit controller retold with ``hidden`` units: unit j is a copy of unit j mod 50 with its
+    output weight divided by the number of copies and its bias moved by a seeded 1e-3, so the commands stay those of
+    a controller the press was trained with and no two units are the same. One unit: the reference's unit of largest
+    |W_out|."""
+    W_inp, b_inp, W_out = (np.asarray(a, np.float64) for a in ctrl_weights())
+    if hidden == 1:
+        j = int(np.abs(W_out[0]).argmax())
+        return tuple(a.astype(np.float32) for a in (W_inp[j:j + 1], b_inp[j:j + 1], 4.0 * W_out[:, j:j + 1]))
+    src = np.arange(hidden) % 50
+    copies = np.bincount(src, minlength=50)[src]
+    b = b_inp[src] + 1e-3 * np.random.default_rng(hidden).standard_normal(hidden)
+    return tuple(a.astype(np.float32) for a in (W_inp[src], b, W_out[:, src] / copies))
+
+
+@pytest.mark.parametrize("hidden", loop_widths())
+def test_single_model_loop_at_other_controller_widths(hidden):
+    """ClosedLoop.run, plain and under process and measurement noise, B = 5 and T = 6: only width 50 runs in the tests
+    above (7 in the bank's). Same bounds as there; the commands must really depend on the controller (they move, and
+    differ between the trajectories)."""
+    assert 1 <= hidden <= _cl_constants()[1]
+    B, T = 5, 6
+    x0, ref, w, v = press_case()
+    x0, ref, w, v = x0[:B], np.ascontiguousarray(ref[:B, 17:17 + T]), w[:B, :T], v[:B, :T]   # the reference changes sign
+    W_inp, b_inp, W_out = widened_controller(hidden)
+    assert W_inp.shape == (hidden, 3) and W_out.shape == (1, hidden)
+    ctrl = fca.FNNModel(3, hidden, 1, 1).to(DEV)
+    with torch.no_grad():
+        ctrl.fc_inp.weight.copy_(torch.tensor(W_inp))
+        ctrl.fc_inp.bias.copy_(torch.tensor(b_inp))
+        ctrl.fc_out.weight.copy_(torch.tensor(W_out))
+    cl = fca.ClosedLoop(ctrl, SCALERS)
+    t = lambda a: torch.tensor(a, device=DEV)
+    for name, ww, vv in (("plain", None, None), ("w+v", w, v)):
+        xr, ur = closed_loop(x0, ref, W_inp, b_inp, W_out, SCALERS["input"][:2], SCALERS["y_dot"], SCALERS["output"],
+                             process_noise=ww, meas_noise=vv)
+        assert np.isfinite(xr).all() and xr[:, :, 1].min() > -0.5
+        assert (ur != 0).mean() >= 0.25 and np.ptp(ur, axis=1).min() > 0       # every trajectory's command moves
+        x, u = cl.run(t(x0), t(ref), process_noise=None if ww is None else t(ww), meas_noise=None if vv is None else t(vv))
+        x, u = x.cpu().numpy(), u.cpu().numpy()
+        assert x.shape == (B, T + 1, 5) and u.shape == (B, T) and np.array_equal(x[:, 0], x0)
+        scale = np.abs(xr).reshape(-1, 5).max(0)
+        err = (np.abs(x - xr).reshape(-1, 5) / scale).max(0)
+        uerr = np.abs(u - ur).max() / np.abs(ur).max()
+        print(f"hidden={hidden} {name}: state err {err}, u err {uerr:.3g}")
+        assert np.all(err < 1e-5), (name, err)
+        assert uerr <= 1e-5, (name, uerr)

@@ -263,3 +263,24 @@ def test_many_workspace_grows_with_models_and_groups():
     assert size(15, 10, False) < size(15, 10) / 2
     # a model's slabs are the single call's: 10 windows x 30 cells x 52 units of h and c per trajectory of a group
     assert per_group > 16 * 10 * 30 * 52 * 2 * 4
+
+
+def test_many_workspace_accepts_ctrl_hidden_up_to_52_and_grows_by_the_models_slabs():
+    """fcr_many_workspace_size: ctrl_hidden 1..52 as in the single-model query (53: FCR_EUNSUPPORTED), and the only slab
+    the width sizes is the M models' partial controller gradients, 5 floats per unit and block of 1024 items."""
+    lib = fca._native.load()
+    out = ctypes.c_size_t(0)
+    M, B, N = 3, 17, 3
+    size = {}
+    for ch in (1, 7, 52):
+        d = dims(B=B, N=N, ctrl_hidden=ch)
+        assert lib.fcr_many_workspace_size(ctypes.byref(d), None, M, 1, ctypes.byref(out)) == 0 and out.value > 0, ch
+        size[ch] = out.value
+    for ch in (0, 53):
+        d = dims(B=B, N=N, ctrl_hidden=ch)
+        assert lib.fcr_many_workspace_size(ctypes.byref(d), None, M, 1, ctypes.byref(out)) == -4, ch
+        assert f"ctrl_hidden={ch}" in lib.fcr_last_error().decode()
+        assert lib.fcr_forward_many(ctypes.byref(d), None, M, None, *([None] * 10), 1, None, 0, None) == -4, ch
+    slab = lambda ch: (4 * M * 1 * ch * 5 + 255) // 256 * 256           # B * N = 51 items: one block per model
+    assert size[7] - size[1] == slab(7) - slab(1) and size[52] - size[1] == slab(52) - slab(1)
+    assert size[52] > size[1]
