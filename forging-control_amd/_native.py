@@ -35,8 +35,15 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_lstm_rollout", "fcr_feasibility_project", "fcr_supervised_epoch", "fcr_many_workspace_size",
            "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many",
            "fcr_closed_loop_run_bank", "fcr_press_nominal", "fcr_plant_rk4_press", "fcr_feasibility_project_press",
-           "fcr_closed_loop_run_bank_press")
+           "fcr_closed_loop_run_bank_press", "fcr_loss_terms_default", "fcr_forward_terms", "fcr_backward_terms",
+           "fcr_forward_many_terms", "fcr_backward_many_terms")
 LOSS_L1, LOSS_MSE = 0, 1
+P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
+
+
+def default_terms_row(alpha):
+    """fcr_loss_terms_default as a row (alpha, p1_lo, p1_hi, p2_lo, p2_hi, w_con)."""
+    return (float(alpha), 0.0, P1_MAX, 0.0, P2_MAX, 1.0)
 OPT_INHERIT, KEEP_AUTO = -2, -1
 INT32_MAX, INT64_MAX = 2**31 - 1, 2**63 - 1
 
@@ -73,6 +80,29 @@ class FcrWeights(ctypes.Structure):
         ("w_ih", ctypes.c_void_p * 3), ("w_hh", ctypes.c_void_p * 3),
         ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p),
     ]
+
+
+class FcrLossTerms(ctypes.Structure):
+    """fcr_loss_terms (include/fcr.h): the loss's alpha, pressure bounds, constraint weight and reference preview."""
+    _fields_ = [
+        ("alpha", ctypes.c_float), ("p1_lo", ctypes.c_float), ("p1_hi", ctypes.c_float), ("p2_lo", ctypes.c_float),
+        ("p2_hi", ctypes.c_float), ("w_con", ctypes.c_float),
+        ("ref", ctypes.c_void_p), ("ref_stride_b", ctypes.c_int64), ("ref_stride_j", ctypes.c_int64),
+        ("table", ctypes.c_void_p), ("table_stride", ctypes.c_int64), ("ref_stride_m", ctypes.c_int64),
+    ]
+
+
+def make_loss_terms(row, ref=None, ref_strides=(0, 0, 0), table=None, table_stride=0) -> FcrLossTerms:
+    """fcr_loss_terms from a row (alpha, p1_lo, p1_hi, p2_lo, p2_hi, w_con), a reference tensor (or None: X's column)
+    with its (model, trajectory, step) element strides, and a device table of rows (or None) for the many calls."""
+    t = FcrLossTerms(*[float(v) for v in row])
+    if ref is not None:
+        t.ref = ref.data_ptr()
+        t.ref_stride_m, t.ref_stride_b, t.ref_stride_j = (int(s) for s in ref_strides)
+    if table is not None:
+        t.table = table.data_ptr()
+        t.table_stride = int(table_stride)
+    return t
 
 
 class FcrWindows(ctypes.Structure):
@@ -227,6 +257,23 @@ def load() -> ctypes.CDLL:
         lib.fcr_forward_many.restype = i32
         lib.fcr_backward_many.argtypes = [ctypes.POINTER(FcrDims), po, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         lib.fcr_backward_many.restype = i32
+        # the loss's terms as data (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the
+        # addition loads without it; calls with terms or a reference preview then raise AttributeError.
+        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_forward_terms"):
+            pt = ctypes.POINTER(FcrLossTerms)
+            lib.fcr_loss_terms_default.argtypes = [pt, ctypes.c_float]
+            lib.fcr_loss_terms_default.restype = None
+            lib.fcr_forward_terms.argtypes = [ctypes.POINTER(FcrDims), po, ctypes.POINTER(FcrWeights), pt,
+                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+            lib.fcr_forward_terms.restype = i32
+            lib.fcr_backward_terms.argtypes = [ctypes.POINTER(FcrDims), po, pt, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+            lib.fcr_backward_terms.restype = i32
+            lib.fcr_forward_many_terms.argtypes = [ctypes.POINTER(FcrDims), po, i32, ctypes.POINTER(FcrWeights), pt,
+                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
+            lib.fcr_forward_many_terms.restype = i32
+            lib.fcr_backward_many_terms.argtypes = [ctypes.POINTER(FcrDims), po, i32, pt, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                    vp, sz, vp]
+            lib.fcr_backward_many_terms.restype = i32
         lib.fcr_fnn_forward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_fnn_forward_many.restype = i32
         lib.fcr_fnn_backward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]

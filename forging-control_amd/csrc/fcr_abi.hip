@@ -127,6 +127,45 @@ int check_lro_dims(const fcr_dims *d) {
     return FCR_OK;
 }
 
+// fcr_loss_terms -> the kernels' Terms (fcr_common.h), checked before any launch. many: d->B is one model's batch
+// and X is stacked (M,B,3), so the default reference's model stride is 3 B.
+int resolve_terms(const char *what, const fcr_dims *d, const fcr_loss_terms *t, const float *X, bool many, Terms *out) {
+    if (!t) return fail(FCR_EINVAL, "%s: terms is NULL", what);
+    Terms tm{};
+    tm.row = TermRow{t->alpha, t->p1_lo, t->p1_hi, t->p2_lo, t->p2_hi, t->w_con};
+    if (!(many && t->table)) {   // (a table's values live on the device: the caller's to check, include/fcr.h)
+        if (!(t->alpha - t->alpha == 0.0f)) return fail(FCR_EINVAL, "%s: terms.alpha=%g must be finite", what, t->alpha);
+        if (t->p1_lo != t->p1_lo || t->p1_hi != t->p1_hi || t->p2_lo != t->p2_lo || t->p2_hi != t->p2_hi ||
+            t->w_con != t->w_con)
+            return fail(FCR_EINVAL, "%s: a loss term is NaN (p1 [%g, %g], p2 [%g, %g], w_con %g)", what, t->p1_lo, t->p1_hi,
+                        t->p2_lo, t->p2_hi, t->w_con);
+        if (t->p1_lo > t->p1_hi) return fail(FCR_EINVAL, "%s: terms.p1_lo=%g is above p1_hi=%g", what, t->p1_lo, t->p1_hi);
+        if (t->p2_lo > t->p2_hi) return fail(FCR_EINVAL, "%s: terms.p2_lo=%g is above p2_hi=%g", what, t->p2_lo, t->p2_hi);
+        if (t->w_con < 0.0f || !(t->w_con - t->w_con == 0.0f))
+            return fail(FCR_EINVAL, "%s: terms.w_con=%g must be finite and >= 0", what, t->w_con);
+    }
+    if (many && t->table) {
+        if (t->table_stride < 0) return fail(FCR_EINVAL, "%s: terms.table_stride=%lld must be >= 0", what, (long long)t->table_stride);
+        tm.table = t->table;
+        tm.table_stride = t->table_stride;
+    }
+    if (t->ref) {
+        if (t->ref_stride_b < 0 || t->ref_stride_j < 0 || (many && t->ref_stride_m < 0))
+            return fail(FCR_EINVAL, "%s: terms.ref strides must be >= 0", what);
+        tm.ref = t->ref;
+        tm.ref_b = t->ref_stride_b;
+        tm.ref_j = t->ref_stride_j;
+        tm.ref_m = many ? t->ref_stride_m : 0;
+    } else {
+        tm.ref = X + (kCtrlIn - 1);   // Functions.py:1392: X[:, -1] in every step
+        tm.ref_b = kCtrlIn;
+        tm.ref_j = 0;
+        tm.ref_m = many ? (long long)kCtrlIn * d->B : 0;
+    }
+    *out = tm;
+    return FCR_OK;
+}
+
 int lstm_weights_ok(const fcr_weights *w) {
     if (!w || !w->fc_w || !w->fc_b) return 0;
     for (int l = 0; l < kLayers; ++l)
@@ -219,12 +258,34 @@ int fcr_workspace_size(const fcr_dims *dims, const fcr_options *opts, int with_b
     return FCR_OK;
 }
 
+void fcr_loss_terms_default(fcr_loss_terms *t, float alpha) {
+    if (!t) return;
+    *t = fcr_loss_terms{};
+    t->alpha = alpha;
+    t->p1_hi = kP1Max;
+    t->p2_hi = kP2Max;
+    t->w_con = 1.0f;
+}
+
 int fcr_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, const float *X, const float *u0,
                 const float *states, const float *noise, float *loss, float *cost, float *command,
                 float *error, float *prediction, float *xhat, int with_backward, void *ws,
                 size_t ws_bytes, void *stream) {
+    if (const int rc = check_dims(d)) return rc;
+    fcr_loss_terms t;
+    fcr_loss_terms_default(&t, d->alpha);
+    return fcr_forward_terms(d, opts, w, &t, X, u0, states, noise, loss, cost, command, error, prediction, xhat,
+                             with_backward, ws, ws_bytes, stream);
+}
+
+int fcr_forward_terms(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, const fcr_loss_terms *terms,
+                      const float *X, const float *u0, const float *states, const float *noise, float *loss, float *cost,
+                      float *command, float *error, float *prediction, float *xhat, int with_backward, void *ws,
+                      size_t ws_bytes, void *stream) {
     int rc = check_dims(d);
     if (rc) return rc;
+    Terms tm;   // (the terms are checked before the pointers: X is not read, only offset)
+    if ((rc = resolve_terms("fcr_forward", d, terms, X, false, &tm))) return rc;
     if (!w || !X || !u0 || !states || !loss || !cost || !command || !error || !prediction || !ws)
         return fail(FCR_EINVAL, "fcr_forward: a required pointer is NULL");
     for (int l = 0; l < kLayers; ++l)
@@ -235,29 +296,41 @@ int fcr_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, cons
     if (is_wide(d)) {
         if ((rc = check_ws("fcr_forward", ws, ws_bytes, wide_workspace(d, with_backward, 0)))) return rc;
         note_kernels(opts, FCR_KERNELS_WIDE);
-        return wide_forward(d, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
+        return wide_forward(d, tm, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
                             (char *)ws, ws_bytes, (hipStream_t)stream);
     }
     if ((rc = check_ws("fcr_forward", ws, ws_bytes, rollout_workspace(d, with_backward)))) return rc;
-    return rollout_forward(d, opts, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
+    return rollout_forward(d, opts, tm, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
                            (char *)ws, (hipStream_t)stream);
 }
 
 int fcr_backward(const fcr_dims *d, fcr_options *opts, const float *X, const float *states, const float *prediction,
                  const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out,
                  void *ws, size_t ws_bytes, void *stream) {
+    if (const int rc = check_dims(d)) return rc;
+    fcr_loss_terms t;
+    fcr_loss_terms_default(&t, d->alpha);
+    return fcr_backward_terms(d, opts, &t, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, ws, ws_bytes,
+                              stream);
+}
+
+int fcr_backward_terms(const fcr_dims *d, fcr_options *opts, const fcr_loss_terms *terms, const float *X,
+                       const float *states, const float *prediction, const float *dloss, float *g_u0, float *g_w_inp,
+                       float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes, void *stream) {
     int rc = check_dims(d);
     if (rc) return rc;
+    Terms tm;
+    if ((rc = resolve_terms("fcr_backward", d, terms, X, false, &tm))) return rc;
     if (!X || !states || !prediction || !dloss || !g_u0 || !g_w_inp || !g_b_inp || !g_w_out || !ws)
         return fail(FCR_EINVAL, "fcr_backward: a required pointer is NULL");
     if (is_wide(d)) {
         if ((rc = check_ws("fcr_backward", ws, ws_bytes, wide_workspace(d, 1, 0)))) return rc;
         note_kernels(opts, FCR_KERNELS_WIDE);
-        return wide_backward(d, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws, ws_bytes,
+        return wide_backward(d, tm, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws, ws_bytes,
                              (hipStream_t)stream);
     }
     if ((rc = check_ws("fcr_backward", ws, ws_bytes, rollout_workspace(d, 1)))) return rc;
-    return rollout_backward(d, opts, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws,
+    return rollout_backward(d, opts, tm, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws,
                             (hipStream_t)stream);
 }
 
@@ -292,8 +365,21 @@ int fcr_forward_many(const fcr_dims *d, fcr_options *opts, int32_t n_models, con
                      const float *u0, const float *states, const float *noise, float *loss, float *cost, float *command,
                      float *error, float *prediction, float *xhat, int with_backward, void *ws, size_t ws_bytes,
                      void *stream) {
+    if (const int rc = many_check("fcr_forward_many", d, opts, n_models)) return rc;
+    fcr_loss_terms t;
+    fcr_loss_terms_default(&t, d->alpha);
+    return fcr_forward_many_terms(d, opts, n_models, w, &t, X, u0, states, noise, loss, cost, command, error, prediction,
+                                  xhat, with_backward, ws, ws_bytes, stream);
+}
+
+int fcr_forward_many_terms(const fcr_dims *d, fcr_options *opts, int32_t n_models, const fcr_weights *w,
+                           const fcr_loss_terms *terms, const float *X, const float *u0, const float *states,
+                           const float *noise, float *loss, float *cost, float *command, float *error, float *prediction,
+                           float *xhat, int with_backward, void *ws, size_t ws_bytes, void *stream) {
     int rc = many_check("fcr_forward_many", d, opts, n_models);
     if (rc) return rc;
+    Terms tm;
+    if ((rc = resolve_terms("fcr_forward_many", d, terms, X, true, &tm))) return rc;
     if (n_models == 0) return FCR_OK;
     if (!w || !X || !u0 || !states || !loss || !cost || !command || !error || !prediction || !ws)
         return fail(FCR_EINVAL, "fcr_forward_many: a required pointer is NULL");
@@ -303,21 +389,34 @@ int fcr_forward_many(const fcr_dims *d, fcr_options *opts, int32_t n_models, con
         return fail(FCR_EINVAL, "fcr_forward_many: a weight pointer is NULL");
     if ((rc = check_ws("fcr_forward_many", ws, ws_bytes, many_workspace(d, n_models, with_backward)))) return rc;
     note_kernels(opts, FCR_KERNELS_SMALL);
-    return many_forward(d, n_models, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
+    return many_forward(d, n_models, tm, w, X, u0, states, noise, loss, cost, command, error, prediction, xhat, with_backward,
                         (char *)ws, (hipStream_t)stream);
 }
 
 int fcr_backward_many(const fcr_dims *d, fcr_options *opts, int32_t n_models, const float *X, const float *states,
                       const float *prediction, const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp,
                       float *g_w_out, void *ws, size_t ws_bytes, void *stream) {
+    if (const int rc = many_check("fcr_backward_many", d, opts, n_models)) return rc;
+    fcr_loss_terms t;
+    fcr_loss_terms_default(&t, d->alpha);
+    return fcr_backward_many_terms(d, opts, n_models, &t, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out,
+                                   ws, ws_bytes, stream);
+}
+
+int fcr_backward_many_terms(const fcr_dims *d, fcr_options *opts, int32_t n_models, const fcr_loss_terms *terms,
+                            const float *X, const float *states, const float *prediction, const float *dloss,
+                            float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes,
+                            void *stream) {
     int rc = many_check("fcr_backward_many", d, opts, n_models);
     if (rc) return rc;
+    Terms tm;
+    if ((rc = resolve_terms("fcr_backward_many", d, terms, X, true, &tm))) return rc;
     if (n_models == 0) return FCR_OK;
     if (!X || !states || !prediction || !dloss || !g_u0 || !g_w_inp || !g_b_inp || !g_w_out || !ws)
         return fail(FCR_EINVAL, "fcr_backward_many: a required pointer is NULL");
     if ((rc = check_ws("fcr_backward_many", ws, ws_bytes, many_workspace(d, n_models, 1)))) return rc;
     note_kernels(opts, FCR_KERNELS_SMALL);
-    return many_backward(d, n_models, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws,
+    return many_backward(d, n_models, tm, X, states, prediction, dloss, g_u0, g_w_inp, g_b_inp, g_w_out, (char *)ws,
                          (hipStream_t)stream);
 }
 

@@ -489,7 +489,8 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
     const bool valid = b < a.B;
     const int bc = valid ? b : a.B - 1;
     const int N = a.N;
-    const float alpha = a.alpha;
+    const TermRow tr = a.tm.row;   // wave-uniform: kernel arguments, in scalar registers
+    const float alpha = tr.alpha;
     // d loss / d (one step-cost term) = dloss / (B N)   (Functions.py:1458, 1463)
     const float wgt = valid ? a.dloss[0] / ((float)a.B * (float)N) : 0.0f;
     const float scq = a.p.wsc[q], sc4 = a.p.wsc[4];   // range guard (fcr_pack.h): d/dv = 2^-s_c d/dv'
@@ -526,19 +527,21 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
     // (w = j+1, t = 9), was stored by the first layer-0 cell of window j+1, at least one cell earlier in this wave's
     // program order.
     struct HeadIn {
-        float x[kOut], p[3], ref;
+        float x[kOut], p[3], ref, ref1;   // ref = r_j (the error's), ref1 = r_{j+1} (the controller call fed by step j)
         f32x2 g[kL];
     };
     auto head_issue = [&](int j, int bcl, HeadIn &hi) {
         const float *xj = a.xhat + ((size_t)bcl * N + j) * kOut, *pj = a.prediction + (size_t)bcl * N + j;
 #pragma unroll
         for (int o = 0; o < kOut; ++o) hi.x[o] = xj[o];
-        hi.ref = a.X[(size_t)bcl * kCtrlIn + 2];
+        const float *rj = a.tm.ref + (long long)bcl * a.tm.ref_b + (long long)j * a.tm.ref_j;
+        hi.ref = hi.ref1 = rj[0];
         hi.p[0] = hi.p[1] = hi.p[2] = 0.0f;
 #pragma unroll
         for (int i = 0; i < kL; ++i) hi.g[i] = f32x2{0.0f, 0.0f};
         if (j <= N - 2) {
             row_issue(kL + j, hi.g);
+            hi.ref1 = rj[a.tm.ref_j];
             hi.p[0] = pj[0];
             hi.p[1] = pj[1];
             if (j + 2 < N) hi.p[2] = pj[2];
@@ -628,8 +631,8 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         const float x0 = hin.x[0], x1 = hin.x[1], x2 = hin.x[2], x3 = hin.x[3];
         // direct cost gradients of step j (Functions.py:1443-1452)
         float d0 = hr.wgt * 2.0f * (x0 - hin.ref);
-        float d1 = hr.wgt * ((-x1 > 0.0f ? -1.0f : 0.0f) + (x1 - kP1Max > 0.0f ? 1.0f : 0.0f));
-        float d2 = hr.wgt * ((-x2 > 0.0f ? -1.0f : 0.0f) + (x2 - kP2Max > 0.0f ? 1.0f : 0.0f));
+        float d1 = hr.wgt * con_grad(tr.p1_lo, tr.p1_hi, tr.w, x1);
+        float d2 = hr.wgt * con_grad(tr.p2_lo, tr.p2_hi, tr.w, x2);
         float d3 = 0.0f;
         if (j <= N - 2) {
             // row 10+j = (xhat_j, u_{j+1}) is complete once windows j+1 .. j+10 are done
@@ -643,9 +646,9 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
             float du = hr.aw * (uj1 - uj);                                    // cmd_{j+1} (aw = 2 alpha wgt)
             if (j + 2 < N) du += hr.aw * (uj1 - hin.p[2]);                    // cmd_{j+2}
             du += g4;
-            // controller backward at (xhat_j[0], xhat_j[3], ref) (Functions.py:1424-1430)
+            // controller backward at (xhat_j[0], xhat_j[3], r_{j+1}) (Functions.py:1424-1430)
             float z[kMS];
-            const float v = fnn_pre(lfnp_j, hr.q, x0, x3, hin.ref, z);
+            const float v = fnn_pre(lfnp_j, hr.q, x0, x3, hin.ref1, z);
             const float dv = (v > -1.0f && v < 1.0f) ? du : 0.0f;            // Hardtanh'
             float dca = 0.0f, dcb = 0.0f;
 #pragma unroll

@@ -24,7 +24,7 @@ constexpr int kMS = 13;          // controller hidden slots (units 4m+q), hidden
 constexpr int kFnpStride = 8;    // floats per (m, q) controller record: W0 W1 W2 b wout 0 0 0
 constexpr int kFwdWaves = 8;     // waves per forward workgroup (2 per SIMD)
 constexpr int kBwdWaves = 8;     // waves per backward workgroup (2 per SIMD)
-constexpr float kP1Max = 2.122366f;  // Functions.py:1411 (32e6 / p1 max_abs_)
+constexpr float kP1Max = 2.122366f;  // Functions.py:1411 (32e6 / p1 max_abs_): the default upper bounds (fcr_loss_terms)
 constexpr float kP2Max = 1.036233f;  // Functions.py:1411 (32e6 / p2 max_abs_)
 
 template <int HS>
@@ -47,9 +47,32 @@ struct Packed {                    // device pointers into the workspace
 //   xw         [wave][j][t][64]               layer-0 window row t of window j (col q, col 4)
 //   dseq       [wave][j][2][t][record]         backward dx of layers 2, 1 (inputs of layers 1, 0)
 //   dxrow      [wave][j][t][64]               backward window-row gradients (col q, col 4)
+// The loss's terms (include/fcr.h fcr_loss_terms) as kernel arguments: wave-uniform, in scalar registers.
+//   row    alpha, the pressure bounds and the constraint's weight of a single-model call
+//   table  many-model kernels: model m's row is table + m * table_stride (6 floats, TermRow's order; stride 0 = one
+//          shared row); null = `row` for every model
+//   ref    the reference of trajectory b (of model m) at horizon step j: ref[m * ref_m + b * ref_b + j * ref_j]
+//          (the default: X + 2 with strides (3 B, 3, 0), the constant X[b, 2])
+struct TermRow {
+    float alpha, p1_lo, p1_hi, p2_lo, p2_hi, w;
+};
+struct Terms {
+    TermRow row;
+    const float *table;
+    long long table_stride;
+    const float *ref;
+    long long ref_m, ref_b, ref_j;
+};
+// model m's row (m workgroup-uniform, so these are scalar loads)
+__device__ __forceinline__ TermRow term_row(const Terms &t, int m) {
+    if (!t.table) return t.row;
+    const float *p = t.table + (long long)m * t.table_stride;
+    return TermRow{p[0], p[1], p[2], p[3], p[4], p[5]};
+}
+
 struct FwdArgs {
     int B, N;
-    float alpha;
+    Terms tm;
     const float *X, *u0, *states, *noise;
     float *cost, *command, *error, *prediction, *xhat_user, *xhat_ws, *loss_part;
     f32x4 *hseq;     // layers 0, 1 always (the next phase's input); layer 2 with `keep`
@@ -61,7 +84,7 @@ struct FwdArgs {
 
 struct BwdArgs {
     int B, N, hidden;
-    float alpha;
+    Terms tm;
     const float *X, *states, *prediction, *xhat, *dloss;
     const f32x4 *hseq, *cseq;
     const f32x2 *xw;
@@ -96,6 +119,16 @@ constexpr float kTwoLog2e = 2.8853900817779268f;
 __device__ __forceinline__ float relu(float x) { return x > 0.0f ? x : 0.0f; }
 __device__ __forceinline__ float sq(float x) { return x * x; }
 __device__ __forceinline__ float hardtanh(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
+// The pressure constraint of one step (Functions.py:1411, 1449) and its derivative by one pressure, with the bounds
+// and the weight as data. At the defaults (0, kP1Max, 0, kP2Max, 1) both give the literal forms' bits: 0 - p and -p
+// differ only in the sign of a zero that relu and the masks drop, and the product with 1 is exact. An infinite bound
+// on its open side gives relu(-inf) = 0 and a false mask.
+__device__ __forceinline__ float con_cost(const TermRow &r, float p1, float p2) {
+    return r.w * (relu(r.p1_lo - p1) + relu(r.p2_lo - p2) + relu(p1 - r.p1_hi) + relu(p2 - r.p2_hi));
+}
+__device__ __forceinline__ float con_grad(float lo, float hi, float w, float p) {
+    return w * ((lo - p > 0.0f ? -1.0f : 0.0f) + (p - hi > 0.0f ? 1.0f : 0.0f));
+}
 __device__ __forceinline__ float sel4(int q, float a, float b, float c, float d) {
     return q == 0 ? a : (q == 1 ? b : (q == 2 ? c : d));
 }

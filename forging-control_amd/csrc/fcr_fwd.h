@@ -167,9 +167,16 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
     const bool valid = b < a.B;
     const int bc = valid ? b : a.B - 1;   // out-of-range lanes recompute the last trajectory
     const int N = a.N;
-    const float alpha = a.alpha;
+    const TermRow tr = a.tm.row;   // wave-uniform: kernel arguments, in scalar registers
+    const float alpha = tr.alpha;
 
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];                 // Functions.py:1392
+    // r_j = ref[b * ref_b + j * ref_j] (Functions.py:1392: X[b, 2] in every window, the default strides): window j's
+    // controller call and error. With ref_j = 0 (no preview) it is the kernel-lifetime register it always was; with a
+    // preview it is reloaded at the top of each window (a wave-uniform branch), where the head's LDS reads go out
+    // beside the load: its latency, about 1 us a window, measured 0.8 % of this kernel when every call paid it, and
+    // holding r_{j+1} ahead in a second register across the cells cost the H <= 32 f16 forward a wave per SIMD
+    // (DESIGN.md §7.12).
+    float ref = a.tm.ref[(long long)bc * a.tm.ref_b];
     const float *st = a.states + (size_t)bc * kL * kIn;
     float w0[kL], w1[kL];                                             // window ring, B-operand layout
     const float scq = a.p.wsc[q], sc4 = a.p.wsc[4];   // range guard (fcr_pack.h): the ring holds v 2^-s_c
@@ -203,6 +210,7 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
     for (int j = 0; j < N; ++j) {
         const unsigned long long st_w0 = fstamp();
         const float *lfnp_j = opaque(lfnp), *lfcp_j = opaque(lfcp), *lfcb_j = opaque(lfcb);
+        if (a.tm.ref_j != 0 && j > 0) ref = a.tm.ref[(long long)bc * a.tm.ref_b + (long long)j * a.tm.ref_j];
         float pred = u0;
         if (j > 0) {                                                   // Functions.py:1421-1434
             float z[kMS];
@@ -369,7 +377,7 @@ __global__ __launch_bounds__(kFwdWaves * kWave, kFwdWaves / 4) void fcr_fwd_kern
         }
         // ---- step cost (Functions.py:1405-1414, 1443-1452) ----
         const float err = sq(xh0 - ref);
-        const float con = relu(-xh1) + relu(-xh2) + relu(xh1 - kP1Max) + relu(xh2 - kP2Max);
+        const float con = con_cost(tr, xh1, xh2);
         tot_sum += (err + cmd_j) + con;
         err_sum += err;
         cmd_sum += cmd_j;

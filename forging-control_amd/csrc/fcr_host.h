@@ -76,7 +76,7 @@ int launch_pack_ctrl(const fcr_weights *w, int CH, float *fcp, float *fcbo, floa
 // loss = sum(part[0..n)) / B in fixed order
 int launch_loss_reduce(const float *part, int n, int B, float *loss, hipStream_t s);
 // The controller's weight gradients from the backward's dv: per-block partials, then their fixed-order sum
-int launch_ctrl_grads(const fcr_dims *d, const float *X, const float *xhat, const float *dv, const float *fnp, float *part,
+int launch_ctrl_grads(const fcr_dims *d, const Terms &tm, const float *xhat, const float *dv, const float *fnp, float *part,
                       int ctrl_blocks, float *g_w_inp, float *g_b_inp, float *g_w_out, hipStream_t s);
 int launch_grad_reduce(const float *part, int blocks, int hidden, float *g_w_inp, float *g_b_inp, float *g_w_out,
                        hipStream_t s);
@@ -85,19 +85,20 @@ int launch_grad_reduce_many(const float *part, int blocks, int hidden, int n_mod
                             float *g_w_out, hipStream_t s);
 int pipe_max_sets();   // the most window sets the pipelined forward runs (fcr_pipe.h)
 size_t rollout_workspace(const fcr_dims *d, int with_backward);
-int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, const float *X, const float *u0,
+// tm: the loss's terms as the kernels take them (fcr_common.h; resolved and checked by fcr_abi.hip)
+int rollout_forward(const fcr_dims *d, fcr_options *opts, const Terms &tm, const fcr_weights *w, const float *X, const float *u0,
                     const float *states, const float *noise, float *loss, float *cost, float *command, float *error,
                     float *prediction, float *xhat, int with_backward, char *base, hipStream_t s);
-int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const float *states, const float *prediction,
+int rollout_backward(const fcr_dims *d, fcr_options *opts, const Terms &tm, const float *X, const float *states, const float *prediction,
                      const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                      hipStream_t s);
 // M controllers side by side through the one-workgroup small-batch kernels (fcr_small.h, MANY); d->B = one model's batch
 bool many_supported(const fcr_dims *d);   // slot tier 8 or 13
 size_t many_workspace(const fcr_dims *d, int n_models, int with_backward);
-int many_forward(const fcr_dims *d, int n_models, const fcr_weights *w, const float *X, const float *u0,
+int many_forward(const fcr_dims *d, int n_models, const Terms &tm, const fcr_weights *w, const float *X, const float *u0,
                  const float *states, const float *noise, float *loss, float *cost, float *command, float *error,
                  float *prediction, float *xhat, int with_backward, char *base, hipStream_t s);
-int many_backward(const fcr_dims *d, int n_models, const float *X, const float *states, const float *prediction,
+int many_backward(const fcr_dims *d, int n_models, const Terms &tm, const float *X, const float *states, const float *prediction,
                   const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                   hipStream_t s);
 
@@ -107,10 +108,10 @@ size_t wide_workspace(const fcr_dims *d, int with_backward, int keep);
 // backward each derive it from the ws_bytes they are given, so they agree with no state between them.
 int wide_keep_fit(const fcr_dims *d, size_t ws_bytes);
 long long wide_default_cap();
-int wide_forward(const fcr_dims *d, const fcr_weights *w, const float *X, const float *u0, const float *states,
+int wide_forward(const fcr_dims *d, const Terms &tm, const fcr_weights *w, const float *X, const float *u0, const float *states,
                  const float *noise, float *loss, float *cost, float *command, float *error, float *prediction,
                  float *xhat, int with_backward, char *base, size_t ws_bytes, hipStream_t s);
-int wide_backward(const fcr_dims *d, const float *X, const float *states, const float *prediction,
+int wide_backward(const fcr_dims *d, const Terms &tm, const float *X, const float *states, const float *prediction,
                   const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                   size_t ws_bytes, hipStream_t s);
 size_t surw_workspace(const fcr_dims *d, int with_backward);

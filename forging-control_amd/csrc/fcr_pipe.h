@@ -121,14 +121,16 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pfwd_kernel(FwdA
     const int N = a.N;
     const int nwin = pipe_windows<S>(N, set);
     const int NC = nwin * kL;   // cells of the workgroup per layer (its windows)
-    const float alpha = a.alpha;
+    const TermRow tr = a.tm.row;   // workgroup-uniform: kernel arguments
+    const float alpha = tr.alpha;
     unsigned *fl = pa.flags + (size_t)grp * kPipeFlags;
     unsigned *fs = fl + set * P::PER_SET;   // this window set's counters
     float *rowbuf = pa.rows + (size_t)grp * N * kTile * kPipeRow;
     auto row_of = [&](int j) { return rowbuf + ((size_t)j * kTile + sl) * kPipeRow; };   // window j's hand-off row
     auto row_ready = [&](int j) { pipe_wait(fl, fl + (j % S) * P::PER_SET + P::ROW, (unsigned)(j / S + 1)); };
 
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];                 // Functions.py:1392
+    // r_j = rref[j * ref_j] (Functions.py:1392: X[b, 2] in every window, the default strides)
+    const float *rref = a.tm.ref + (long long)bc * a.tm.ref_b;
     const float *st = a.states + (size_t)bc * kL * kIn;
     const float scq = a.p.wsc[q], sc4 = a.p.wsc[4];
     const float u0 = a.u0[bc];
@@ -244,6 +246,8 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pfwd_kernel(FwdA
     bool have_a = false, have_n = false;
     for (int i = 0; i < nwin; ++i) {
         const int j = set + S * i;
+        // r_j (the error's) and r_{j+1} (the next controller call's), requested here: their latency lies under the cells
+        const float ref = rref[(long long)j * a.tm.ref_j], ref1 = rref[(long long)(j + 1 < N ? j + 1 : j) * a.tm.ref_j];
         for (int t = 0; t < kL; ++t) {
             const int m = i * kL + t, n = j * kL + t;
             if (!have_a) {
@@ -318,11 +322,11 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pfwd_kernel(FwdA
             if (a.xhat_user) a.xhat_user[((size_t)b * N + j) * kOut + q] = mine;
         }
         const float err = sq(xh0 - ref);                              // Functions.py:1405-1414, 1443-1452
-        const float con = relu(-xh1) + relu(-xh2) + relu(xh1 - kP1Max) + relu(xh2 - kP2Max);
+        const float con = con_cost(tr, xh1, xh2);
         float un = 0.0f;
         if (j + 1 < N) {                                               // Functions.py:1421-1434
             float z[kMS];
-            un = hardtanh(fnn_pre(lfnp_j, q, xh0, xh3, ref, z));
+            un = hardtanh(fnn_pre(lfnp_j, q, xh0, xh3, ref1, z));
             if (lead && valid && q == 0) a.prediction[(size_t)b * N + j + 1] = un;   // Functions.py:1466
         }
         if (lead) {   // the hand-off row of window j (write-through; only this wave stores it), then its counter
@@ -417,9 +421,10 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pbwd_kernel(BwdA
     const bool lead = w == 0;
     const int bc = valid ? b : a.B - 1;
     const int N = a.N;
-    const float alpha = a.alpha;
+    const TermRow tr = a.tm.row;   // workgroup-uniform: kernel arguments
+    const float alpha = tr.alpha;
     const float wgt = valid ? a.dloss[0] / ((float)a.B * (float)N) : 0.0f;   // Functions.py:1458, 1463
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];
+    const float *rref = a.tm.ref + (long long)bc * a.tm.ref_b;
     const float s84 = a.states[(size_t)bc * kL * kIn + (kL - 2) * kIn + 4];
     const float *pred = a.prediction + (size_t)bc * N;
     const float *xh = a.xhat + (size_t)bc * N * kOut;
@@ -492,9 +497,11 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pbwd_kernel(BwdA
             const float *lfnp_j = opaque(lfnp), *lfcp_j = opaque(lfcp);
             const float x0 = xh[j * kOut + 0], x1 = xh[j * kOut + 1], x2 = xh[j * kOut + 2], x3 = xh[j * kOut + 3];
             const float uj = pred[j], uj1 = pred[j + 1 < N ? j + 1 : j], uj2 = pred[j + 2 < N ? j + 2 : j];
+            // r_j (the error's) and r_{j+1} (the controller call fed by step j)
+            const float ref = rref[(long long)j * a.tm.ref_j], ref1 = rref[(long long)(j + 1 < N ? j + 1 : j) * a.tm.ref_j];
             float d0 = wgt * 2.0f * (x0 - ref);
-            float d1 = wgt * ((-x1 > 0.0f ? -1.0f : 0.0f) + (x1 - kP1Max > 0.0f ? 1.0f : 0.0f));
-            float d2 = wgt * ((-x2 > 0.0f ? -1.0f : 0.0f) + (x2 - kP2Max > 0.0f ? 1.0f : 0.0f));
+            float d1 = wgt * con_grad(tr.p1_lo, tr.p1_hi, tr.w, x1);
+            float d2 = wgt * con_grad(tr.p2_lo, tr.p2_hi, tr.w, x2);
             float d3 = 0.0f;
             if (j <= N - 2) {
                 // row 10 + j sums dx(v, 10 + j - v) over windows v = j + 1 .. j + 10: each set's latest is among
@@ -510,7 +517,7 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_pbwd_kernel(BwdA
                 if (j + 2 < N) du += 2.0f * alpha * wgt * (uj1 - uj2);
                 du += g4;
                 float z[kMS];
-                const float v = fnn_pre(lfnp_j, q, x0, x3, ref, z);
+                const float v = fnn_pre(lfnp_j, q, x0, x3, ref1, z);
                 const float dv = (v > -1.0f && v < 1.0f) ? du : 0.0f;
                 float dca = 0.0f, dcb = 0.0f;
 #pragma unroll

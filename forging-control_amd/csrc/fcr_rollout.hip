@@ -334,11 +334,11 @@ int launch_range(const fcr_dims *d, const float *states, const float *u0, const 
 }
 
 // The controller's weight gradients from the backward's dv: per-block partials, then their fixed-order sum
-int launch_ctrl_grads(const fcr_dims *d, const float *X, const float *xhat, const float *dv, const float *fnp, float *part,
+int launch_ctrl_grads(const fcr_dims *d, const Terms &tm, const float *xhat, const float *dv, const float *fnp, float *part,
                       int ctrl_blocks, float *g_w_inp, float *g_b_inp, float *g_w_out, hipStream_t s) {
     const bool one = ctrl_blocks == 1;   // one block writes the gradients itself (grad_out5)
-    hipLaunchKernelGGL(ctrl_grad_kernel, dim3(ctrl_blocks), dim3(kCtrlBlock), 0, s, X, xhat, dv, fnp, d->B, d->N,
-                       d->ctrl_hidden, part, one ? g_w_inp : nullptr, one ? g_b_inp : nullptr, one ? g_w_out : nullptr);
+    hipLaunchKernelGGL(ctrl_grad_kernel, dim3(ctrl_blocks), dim3(kCtrlBlock), 0, s, tm.ref, tm.ref_b, tm.ref_j, xhat, dv,
+                       fnp, d->B, d->N, d->ctrl_hidden, part, one ? g_w_inp : nullptr, one ? g_b_inp : nullptr, one ? g_w_out : nullptr);
     if (const int rc = launch_check("ctrl_grad_kernel")) return rc;
     if (one) return FCR_OK;
     return launch_grad_reduce(part, ctrl_blocks, d->ctrl_hidden, g_w_inp, g_b_inp, g_w_out, s);
@@ -368,7 +368,7 @@ int pipe_max_sets() { return Pipe<13>::MAX_SETS; }
 
 size_t rollout_workspace(const fcr_dims *d, int with_backward) { return make_layout(d, with_backward).total; }
 
-int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, const float *X, const float *u0,
+int rollout_forward(const fcr_dims *d, fcr_options *opts, const Terms &tm, const fcr_weights *w, const float *X, const float *u0,
                     const float *states, const float *noise, float *loss, float *cost, float *command, float *error,
                     float *prediction, float *xhat, int with_backward, char *base, hipStream_t s) {
     int rc;
@@ -383,7 +383,7 @@ int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, 
     FwdArgs fa{};
     fa.B = d->B;
     fa.N = d->N;
-    fa.alpha = d->alpha;
+    fa.tm = tm;
     fa.X = X;
     fa.u0 = u0;
     fa.states = states;
@@ -428,7 +428,7 @@ int rollout_forward(const fcr_dims *d, fcr_options *opts, const fcr_weights *w, 
     return launch_loss_reduce(fa.loss_part, small ? L.nw : L.nw_pad, d->B, loss, s);
 }
 
-int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const float *states, const float *prediction,
+int rollout_backward(const fcr_dims *d, fcr_options *opts, const Terms &tm, const float *X, const float *states, const float *prediction,
                      const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                      hipStream_t s) {
     int rc;
@@ -437,7 +437,7 @@ int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const
     ba.B = d->B;
     ba.N = d->N;
     ba.hidden = d->ctrl_hidden;
-    ba.alpha = d->alpha;
+    ba.tm = tm;
     ba.X = X;
     ba.states = states;
     ba.prediction = prediction;
@@ -471,7 +471,7 @@ int rollout_backward(const fcr_dims *d, fcr_options *opts, const float *X, const
         }
     }
     if (rc) return rc;
-    return launch_ctrl_grads(d, X, ba.xhat, ba.dv, ba.p.fnp, (float *)(base + L.fnn_part), L.ctrl_blocks, g_w_inp, g_b_inp,
+    return launch_ctrl_grads(d, tm, ba.xhat, ba.dv, ba.p.fnp, (float *)(base + L.fnn_part), L.ctrl_blocks, g_w_inp, g_b_inp,
                              g_w_out, s);
 }
 
@@ -545,7 +545,7 @@ size_t many_workspace(const fcr_dims *d, int n_models, int with_backward) {
     return make_many(d, n_models, with_backward).total;
 }
 
-int many_forward(const fcr_dims *d, int M, const fcr_weights *w, const float *X, const float *u0, const float *states,
+int many_forward(const fcr_dims *d, int M, const Terms &tm, const fcr_weights *w, const float *X, const float *u0, const float *states,
                  const float *noise, float *loss, float *cost, float *command, float *error, float *prediction,
                  float *xhat, int with_backward, char *base, hipStream_t s) {
     int rc;
@@ -564,7 +564,7 @@ int many_forward(const fcr_dims *d, int M, const fcr_weights *w, const float *X,
     FwdArgs fa{};
     fa.B = d->B;
     fa.N = d->N;
-    fa.alpha = d->alpha;
+    fa.tm = tm;
     fa.X = X;
     fa.u0 = u0;
     fa.states = states;
@@ -591,7 +591,7 @@ int many_forward(const fcr_dims *d, int M, const fcr_weights *w, const float *X,
     return launch_check("loss_reduce_many_kernel");
 }
 
-int many_backward(const fcr_dims *d, int M, const float *X, const float *states, const float *prediction,
+int many_backward(const fcr_dims *d, int M, const Terms &tm, const float *X, const float *states, const float *prediction,
                   const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                   hipStream_t s) {
     int rc;
@@ -600,7 +600,7 @@ int many_backward(const fcr_dims *d, int M, const float *X, const float *states,
     ba.B = d->B;
     ba.N = d->N;
     ba.hidden = d->ctrl_hidden;
-    ba.alpha = d->alpha;
+    ba.tm = tm;
     ba.X = X;
     ba.states = states;
     ba.prediction = prediction;
@@ -622,7 +622,8 @@ int many_backward(const fcr_dims *d, int M, const float *X, const float *states,
     if (rc) return rc;
     float *part = (float *)(base + L.fnn_part);
     const bool one = L.ctrl_blocks == 1;   // one block per model writes that model's gradients itself (grad_out5)
-    hipLaunchKernelGGL(ctrl_grad_many_kernel, dim3(L.ctrl_blocks, M), dim3(kCtrlBlock), 0, s, X, ba.xhat, (const float *)ba.dv,
+    hipLaunchKernelGGL(ctrl_grad_many_kernel, dim3(L.ctrl_blocks, M), dim3(kCtrlBlock), 0, s, tm.ref, tm.ref_m, tm.ref_b, tm.ref_j,
+                       ba.xhat, (const float *)ba.dv,
                        ba.p.fnp, d->B, d->N, d->ctrl_hidden, part, L.ctrl_blocks, one ? g_w_inp : nullptr,
                        one ? g_b_inp : nullptr, one ? g_w_out : nullptr);
     if ((rc = launch_check("ctrl_grad_many_kernel"))) return rc;

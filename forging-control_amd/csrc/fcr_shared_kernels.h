@@ -86,7 +86,9 @@ __global__ void loss_reduce_many_kernel(const float *part, int gpm, int B, float
 // the backward kernel stored per (trajectory, step): z = W_inp·[x0, x3, ref] + b is recomputed from
 // the stored xhat with the same arithmetic as fnn_pre; dz = dv·w_out·1[z>0]. One block per chunk of
 // (trajectory, step) items; a wave's lanes are the hidden units; fixed-order sums everywhere.
-__device__ __forceinline__ void ctrl_grad_block(const float *X, const float *xhat, const float *dv, const float *fnp,
+// The call fed by step j is u_{j+1}'s, so its reference is r_{j+1} = ref[b * ref_b + (j + 1) * ref_j] (the default:
+// X + 2 with strides (3, 0)); the last step feeds no call (dv = 0) and reads r_{N-1}, in bounds.
+__device__ __forceinline__ void ctrl_grad_block(const float *ref, long long ref_b, long long ref_j, const float *xhat, const float *dv, const float *fnp,
                                                 int B, int N, int hidden, float *part, float *gwi, float *gbi,
                                                 float *gwo) {
     __shared__ float sx0[kCtrlItems], sx3[kCtrlItems], sref[kCtrlItems], sdv[kCtrlItems];
@@ -99,7 +101,8 @@ __device__ __forceinline__ void ctrl_grad_block(const float *X, const float *xha
         const int bb = (int)(it / N);
         sx0[i] = xhat[it * kOut + 0];
         sx3[i] = xhat[it * kOut + 3];
-        sref[i] = X[(size_t)bb * kCtrlIn + 2];
+        const int jn = (int)(it - (long long)bb * N) + 1;
+        sref[i] = ref[bb * ref_b + (jn < N ? jn : N - 1) * ref_j];
         sdv[i] = dv[it];
     }
     __syncthreads();
@@ -133,20 +136,23 @@ __device__ __forceinline__ void ctrl_grad_block(const float *X, const float *xha
         }
     }
 }
-__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_kernel(const float *X, const float *xhat, const float *dv,
+__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_kernel(const float *ref, long long ref_b, long long ref_j,
+                                                               const float *xhat, const float *dv,
                                                                const float *fnp, int B, int N, int hidden,
                                                                float *part, float *gwi = nullptr,
                                                                float *gbi = nullptr, float *gwo = nullptr) {
-    ctrl_grad_block(X, xhat, dv, fnp, B, N, hidden, part, gwi, gbi, gwo);
+    ctrl_grad_block(ref, ref_b, ref_j, xhat, dv, fnp, B, N, hidden, part, gwi, gbi, gwo);
 }
 // M models (fcr_backward_many): blockIdx.y = m runs ctrl_grad_kernel's blocks over model m's B * N items of the stacked
-// (M, B, ...) arrays with that model's records; `blocks` = the blocks per model (the stride of the partials)
-__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_many_kernel(const float *X, const float *xhat, const float *dv,
+// (M, B, ...) arrays with that model's records; `blocks` = the blocks per model (the stride of the partials); model
+// m's references start at ref + m * ref_m
+__global__ __launch_bounds__(kCtrlBlock) void ctrl_grad_many_kernel(const float *ref, long long ref_m, long long ref_b,
+                                                                    long long ref_j, const float *xhat, const float *dv,
                                                                     const float *fnp, int B, int N, int hidden,
                                                                     float *part, int blocks, float *gwi, float *gbi,
                                                                     float *gwo) {
     const size_t m = blockIdx.y, rows = m * B;
-    ctrl_grad_block(X + rows * kCtrlIn, xhat + rows * N * kOut, dv + rows * N, fnp + m * (kMS * 4 * kFnpStride), B, N, hidden,
+    ctrl_grad_block(ref + (long long)m * ref_m, ref_b, ref_j, xhat + rows * N * kOut, dv + rows * N, fnp + m * (kMS * 4 * kFnpStride), B, N, hidden,
                     part + m * blocks * hidden * 5, gwi ? gwi + m * hidden * kCtrlIn : nullptr,
                     gwi ? gbi + m * hidden : nullptr, gwi ? gwo + m * hidden : nullptr);
 }

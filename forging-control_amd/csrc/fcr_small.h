@@ -280,9 +280,12 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sfwd_kernel(FwdA
     const bool lead = w == 0;     // writes the per-trajectory outputs
     const int bc = valid ? b : mi.row0(a.B) + a.B - 1;
     const int N = a.N;
-    const float alpha = a.alpha;
-
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];                 // Functions.py:1392
+    const TermRow tr = term_row(a.tm, mi.model());   // workgroup-uniform (MANY: model m's row of the table)
+    const float alpha = tr.alpha;
+    // r_j = rref[j * ref_j] (Functions.py:1392: X[b, 2] in every window, the default strides). Window j's controller
+    // call and error use r_j; it is loaded one window ahead, so its latency lies under the window's cells.
+    const float *rref = a.tm.ref + (long long)mi.model() * a.tm.ref_m + (long long)(bc - mi.row0(a.B)) * a.tm.ref_b;
+    float ref = rref[0];
     const float *st = a.states + (size_t)bc * kL * kIn;
     float w0[kL], w1[kL];
     const float scq = a.p.wsc[q], sc4 = a.p.wsc[4];
@@ -315,6 +318,7 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sfwd_kernel(FwdA
     for (int j = 0; j < N; ++j) {
         const unsigned long long sw0 = fstamp();
         const float *lfnp_j = opaque(lfnp), *lfcp_j = opaque(lfcp), *lfcb_j = opaque(lfcb);
+        const float ref_next = rref[(long long)(j + 1 < N ? j + 1 : j) * a.tm.ref_j];
         float pred = u0;
         if (j > 0) {                                                   // Functions.py:1421-1434
             float z[kMS];
@@ -434,10 +438,11 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sfwd_kernel(FwdA
             if (a.xhat_user) a.xhat_user[((size_t)b * N + j) * kOut + q] = mine;
         }
         const float err = sq(xh0 - ref);                              // Functions.py:1405-1414, 1443-1452
-        const float con = relu(-xh1) + relu(-xh2) + relu(xh1 - kP1Max) + relu(xh2 - kP2Max);
+        const float con = con_cost(tr, xh1, xh2);
         tot_sum += (err + cmd_j) + con;
         err_sum += err;
         cmd_sum += cmd_j;
+        ref = ref_next;
         if (FCR_STAMP) sc[4] += fstamp() - sr0;   // readout and costs
     }
     const float cost = tot_sum / (float)N;                             // Functions.py:1458-1460
@@ -950,9 +955,10 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sbwd_kernel(BwdA
     const bool lead = w == 0;
     const int bc = valid ? b : mi.row0(a.B) + a.B - 1;
     const int N = a.N;
-    const float alpha = a.alpha;
+    const TermRow tr = term_row(a.tm, mi.model());   // workgroup-uniform (MANY: model m's row of the table)
+    const float alpha = tr.alpha;
     const float wgt = valid ? a.dloss[mi.model()] / ((float)a.B * (float)N) : 0.0f;   // Functions.py:1458, 1463
-    const float ref = a.X[(size_t)bc * kCtrlIn + 2];
+    const float *rref = a.tm.ref + (long long)mi.model() * a.tm.ref_m + (long long)(bc - mi.row0(a.B)) * a.tm.ref_b;
     const float s84 = a.states[(size_t)bc * kL * kIn + (kL - 2) * kIn + 4];
     const float *pred = a.prediction + (size_t)bc * N;
     const float *xh = a.xhat + (size_t)bc * N * kOut;
@@ -1011,12 +1017,14 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sbwd_kernel(BwdA
         // the window head's global loads go out before the refill's barriers, which cover their latency
         const float x0 = xh[j * kOut + 0], x1 = xh[j * kOut + 1], x2 = xh[j * kOut + 2], x3 = xh[j * kOut + 3];
         const float uj = pred[j], uj1 = pred[j + 1 < N ? j + 1 : j], uj2 = pred[j + 2 < N ? j + 2 : j];
+        // r_j (the error's) and r_{j+1} (the controller call fed by step j)
+        const float ref = rref[(long long)j * a.tm.ref_j], ref1 = rref[(long long)(j + 1 < N ? j + 1 : j) * a.tm.ref_j];
         const f32x2 Gr = j <= N - 2 ? row_grad(kL + j) : f32x2{0.0f, 0.0f};
         small_fill<I1::BYTES, NQ>(lw, a.p.img[2]);
         const unsigned long long th1 = stamp_now();
         float d0 = wgt * 2.0f * (x0 - ref);                             // Functions.py:1443-1452
-        float d1 = wgt * ((-x1 > 0.0f ? -1.0f : 0.0f) + (x1 - kP1Max > 0.0f ? 1.0f : 0.0f));
-        float d2 = wgt * ((-x2 > 0.0f ? -1.0f : 0.0f) + (x2 - kP2Max > 0.0f ? 1.0f : 0.0f));
+        float d1 = wgt * con_grad(tr.p1_lo, tr.p1_hi, tr.w, x1);
+        float d2 = wgt * con_grad(tr.p2_lo, tr.p2_hi, tr.w, x2);
         float d3 = 0.0f;
         if (j <= N - 2) {
             d0 += __shfl(Gr[0], sl);
@@ -1028,7 +1036,7 @@ __global__ __launch_bounds__(Small<HS>::NQ * kWave, 1) void fcr_sbwd_kernel(BwdA
             if (j + 2 < N) du += 2.0f * alpha * wgt * (uj1 - uj2);
             du += g4;
             float z[kMS];                                               // Functions.py:1424-1430
-            const float v = fnn_pre(lfnp_j, q, x0, x3, ref, z);
+            const float v = fnn_pre(lfnp_j, q, x0, x3, ref1, z);
             const float dv = (v > -1.0f && v < 1.0f) ? du : 0.0f;
             float dca = 0.0f, dcb = 0.0f;
 #pragma unroll

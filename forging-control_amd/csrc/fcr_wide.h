@@ -22,7 +22,7 @@ namespace fcr {
 
 struct WideArgs {
     int B, N, H, CH;
-    float alpha;
+    Terms tm;   // the loss's terms (fcr_common.h): tm.row and tm.ref with its (b, j) strides
     const float *X, *u0, *states, *noise;
     const float *fcw, *fcb, *cwi, *cbi, *cwo;
     float *xhat, *pred, *tot, *cmd, *err;
@@ -53,6 +53,11 @@ __device__ __forceinline__ float wide_fnn(const WideArgs &a, float x0, float x3,
     return v;
 }
 
+// r_j of trajectory b (Functions.py:1392: X[b, 2] at every j, the default strides)
+__device__ __forceinline__ float wide_ref(const WideArgs &a, int b, int j) {
+    return a.tm.ref[(long long)b * a.tm.ref_b + (long long)j * a.tm.ref_j];
+}
+
 // extended window row r of trajectory b: rows 0..9 = states (row 9 col 4 = u0), row 10+m = (xhat_m, u_{m+1})
 __device__ __forceinline__ float ext_row(const WideArgs &a, int b, int r, int col) {
     if (r < kL) {
@@ -70,18 +75,18 @@ __global__ void wide_window_kernel(WideArgs a, int j) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
     if (CTRL) {
-        const float ref = a.X[(size_t)b * kCtrlIn + 2];
+        const float ref = wide_ref(a, b, j);   // r_j: u_j = controller(xhat_{j-1}, r_j)
         float u, cmd;
         if (j == 0) {
             u = a.u0[b];
-            cmd = a.alpha * sq(a.states[((size_t)b * kL + kL - 2) * kIn + kIn - 1] - u);
+            cmd = a.tm.row.alpha * sq(a.states[((size_t)b * kL + kL - 2) * kIn + kIn - 1] - u);
             a.tot[b] = cmd;
             a.cmd[b] = cmd;
             a.err[b] = 0.0f;
         } else {
             const float *xh = a.xhat + ((size_t)b * a.N + j - 1) * kOut;
             u = hardtanh(wide_fnn(a, xh[0], xh[3], ref));
-            cmd = a.alpha * sq(a.pred[(size_t)b * a.N + j - 1] - u);
+            cmd = a.tm.row.alpha * sq(a.pred[(size_t)b * a.N + j - 1] - u);
             a.tot[b] += cmd;
             a.cmd[b] += cmd;
         }
@@ -133,9 +138,9 @@ __global__ void wide_readout_kernel(WideArgs a, int j, const float *__restrict__
         xo[o] += a.fcb[o] + (a.noise ? a.noise[((size_t)b * a.N + j) * kOut + o] : 0.0f);
         a.xhat[((size_t)b * a.N + j) * kOut + o] = xo[o];
     }
-    const float ref = a.X[(size_t)b * kCtrlIn + 2];
+    const float ref = wide_ref(a, b, j);
     const float err = sq(xo[0] - ref);
-    const float con = relu(-xo[1]) + relu(-xo[2]) + relu(xo[1] - kP1Max) + relu(xo[2] - kP2Max);
+    const float con = con_cost(a.tm.row, xo[1], xo[2]);
     a.tot[b] += err + con;
     a.err[b] += err;
 }
@@ -158,11 +163,13 @@ __global__ void wide_finish_kernel(WideArgs a, float *cost, float *command, floa
 __device__ __forceinline__ void wide_head_dxhat(const WideArgs &a, int j, int b, float (&d)[kOut]) {
     const int N = a.N;
     const float wgt = a.dloss[0] / ((float)a.B * (float)N);
-    const float ref = a.X[(size_t)b * kCtrlIn + 2];
+    const TermRow &tr = a.tm.row;
+    // r_j (the error's) and r_{j+1} (the controller call fed by step j)
+    const float ref = wide_ref(a, b, j), ref1 = wide_ref(a, b, j + 1 < N ? j + 1 : j);
     const float *xh = a.xhat + ((size_t)b * N + j) * kOut;
     float d0 = wgt * 2.0f * (xh[0] - ref);
-    float d1 = wgt * ((-xh[1] > 0.0f ? -1.0f : 0.0f) + (xh[1] - kP1Max > 0.0f ? 1.0f : 0.0f));
-    float d2 = wgt * ((-xh[2] > 0.0f ? -1.0f : 0.0f) + (xh[2] - kP2Max > 0.0f ? 1.0f : 0.0f));
+    float d1 = wgt * con_grad(tr.p1_lo, tr.p1_hi, tr.w, xh[1]);
+    float d2 = wgt * con_grad(tr.p2_lo, tr.p2_hi, tr.w, xh[2]);
     float d3 = 0.0f;
     if (j <= N - 2) {
         const float *G = a.rowg + ((size_t)(kL + j) * a.B + b) * kIn;
@@ -171,14 +178,14 @@ __device__ __forceinline__ void wide_head_dxhat(const WideArgs &a, int j, int b,
         d2 += G[2];
         d3 += G[3];
         const float *pr = a.pred + (size_t)b * N;
-        float du = 2.0f * a.alpha * wgt * (pr[j + 1] - pr[j]);
-        if (j + 2 < N) du += 2.0f * a.alpha * wgt * (pr[j + 1] - pr[j + 2]);
+        float du = 2.0f * a.tm.row.alpha * wgt * (pr[j + 1] - pr[j]);
+        if (j + 2 < N) du += 2.0f * a.tm.row.alpha * wgt * (pr[j + 1] - pr[j + 2]);
         du += G[4];
-        const float v = wide_fnn(a, xh[0], xh[3], ref);
+        const float v = wide_fnn(a, xh[0], xh[3], ref1);
         const float dv = (v > -1.0f && v < 1.0f) ? du : 0.0f;
         float dca = 0.0f, dcb = 0.0f;
         for (int k = 0; k < a.CH; ++k) {
-            const float z = a.cwi[k * kCtrlIn + 0] * xh[0] + a.cwi[k * kCtrlIn + 1] * xh[3] + a.cwi[k * kCtrlIn + 2] * ref + a.cbi[k];
+            const float z = a.cwi[k * kCtrlIn + 0] * xh[0] + a.cwi[k * kCtrlIn + 1] * xh[3] + a.cwi[k * kCtrlIn + 2] * ref1 + a.cbi[k];
             const float dz = z > 0.0f ? dv * a.cwo[k] : 0.0f;
             dca += dz * a.cwi[k * kCtrlIn + 0];
             dcb += dz * a.cwi[k * kCtrlIn + 1];
@@ -243,8 +250,8 @@ __global__ void wide_gu0_kernel(WideArgs a, float *g_u0) {
     const float wgt = a.dloss[0] / ((float)a.B * (float)a.N);
     const float *pr = a.pred + (size_t)b * a.N;
     const float s84 = a.states[((size_t)b * kL + kL - 2) * kIn + kIn - 1];
-    float du0 = 2.0f * a.alpha * wgt * (pr[0] - s84);
-    if (a.N > 1) du0 += 2.0f * a.alpha * wgt * (pr[0] - pr[1]);
+    float du0 = 2.0f * a.tm.row.alpha * wgt * (pr[0] - s84);
+    if (a.N > 1) du0 += 2.0f * a.tm.row.alpha * wgt * (pr[0] - pr[1]);
     g_u0[b] = a.rowg[((size_t)(kL - 1) * a.B + b) * kIn + kIn - 1] + du0;
 }
 

@@ -176,7 +176,6 @@ WideArgs wide_args(const fcr_dims *d, const WideLayout &L, char *base) {
     a.N = d->N;
     a.H = L.Hp;   // every wide kernel runs at the padded size
     a.CH = d->ctrl_hidden;
-    a.alpha = d->alpha;
     a.fcw = (const float *)(base + L.fcw);
     a.fcb = (const float *)(base + L.fcb);
     a.cwi = (const float *)(base + L.cwi);
@@ -548,7 +547,7 @@ long long wide_default_cap() {
     return cap_of[dev];
 }
 
-int wide_forward(const fcr_dims *d, const fcr_weights *w, const float *X, const float *u0, const float *states,
+int wide_forward(const fcr_dims *d, const Terms &tm, const fcr_weights *w, const float *X, const float *u0, const float *states,
                  const float *noise, float *loss, float *cost, float *command, float *error, float *prediction,
                  float *xhat, int with_backward, char *base, size_t ws_bytes, hipStream_t s) {
     const WideLayout L = make_wide(d, with_backward, with_backward ? wide_keep_fit(d, ws_bytes) : 0);
@@ -568,6 +567,7 @@ int wide_forward(const fcr_dims *d, const fcr_weights *w, const float *X, const 
         return rc;
     if ((rc = wide_pack(w, d->H, L, kPkFw | kPkFc | (with_backward ? kPkBwd : 0), base, (const float *)(base + L.wsc), s))) return rc;
     WideArgs a = wide_args(d, L, base);
+    a.tm = tm;
     a.X = X;
     a.u0 = u0;
     a.states = states;
@@ -594,13 +594,14 @@ int wide_forward(const fcr_dims *d, const fcr_weights *w, const float *X, const 
     return launch_loss_reduce(cost, d->B, d->B, loss, s);
 }
 
-int wide_backward(const fcr_dims *d, const float *X, const float *states, const float *prediction,
+int wide_backward(const fcr_dims *d, const Terms &tm, const float *X, const float *states, const float *prediction,
                   const float *dloss, float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out, char *base,
                   size_t ws_bytes, hipStream_t s) {
     const WideLayout L = make_wide(d, 1, wide_keep_fit(d, ws_bytes));
     const int B = d->B, nb = (B + 255) / 256;
     int rc;
     WideArgs a = wide_args(d, L, base);
+    a.tm = tm;
     a.X = X;
     a.states = states;
     a.pred = (float *)prediction;
@@ -629,7 +630,7 @@ int wide_backward(const fcr_dims *d, const float *X, const float *states, const 
     }
     hipLaunchKernelGGL(wide_gu0_kernel, dim3(nb), dim3(256), 0, s, a, g_u0);
     if ((rc = launch_check("wide_gu0_kernel"))) return rc;
-    return launch_ctrl_grads(d, X, a.xhat, a.dv, (const float *)(base + L.fnp), (float *)(base + L.fnn_part), L.ctrl_blocks,
+    return launch_ctrl_grads(d, tm, a.xhat, a.dv, (const float *)(base + L.fnp), (float *)(base + L.fnn_part), L.ctrl_blocks,
                              g_w_inp, g_b_inp, g_w_out, s);
 }
 

@@ -27,6 +27,18 @@ def _dev_table(t, name, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def reference_preview(X_table, idx, traj_len: int, horizon: int):
+    """The reference over the horizon of the windows ``idx``: ``ref_h[b, j] = X_table[min(i + j, last row of i's
+    trajectory), 2]`` for ``i = idx[b]``, ``j = 0 .. horizon-1`` — the table's reference column read ahead, held at the
+    trajectory's last row (the clamp of the target ``y[min(i + 1, T - 1)]``). Torch indexing on ``X_table``'s device;
+    an index outside the table is clamped into it (``gather(check=True)`` reports those)."""
+    idx = torch.as_tensor(idx, device=X_table.device).to(torch.int64).reshape(-1)
+    idx = idx.clamp(0, X_table.shape[0] - 1)
+    last = (idx // traj_len) * traj_len + (traj_len - 1)
+    rows = torch.minimum(idx.unsqueeze(1) + torch.arange(int(horizon), device=X_table.device), last.unsqueeze(1))
+    return X_table[:, 2][rows].contiguous()
+
+
 class SequenceWindows:
     """ConcatDataset of SequenceDataset (Functions.py:92-132) over trajectories of ``traj_len`` rows.
 
@@ -61,9 +73,11 @@ class SequenceWindows:
     def __len__(self):
         return self.X.shape[0]
 
-    def gather(self, idx, check: bool = True):
+    def gather(self, idx, check: bool = True, preview: int | None = None):
         """(x (B,nx), y (B,ny), z (B,lookback,nz)) for global indices idx (B,). ``check`` raises
-        IndexError for indices outside [0, len) (one device->host read of the kernel's counter)."""
+        IndexError for indices outside [0, len) (one device->host read of the kernel's counter). ``preview=N`` adds a
+        fourth element, the reference over the next N steps ``ref_h (B,N)`` (:func:`reference_preview`), which
+        ``MPCLoss.forward`` takes as ``ref_horizon``."""
         idx = torch.as_tensor(idx, device=self.device).to(torch.int64).reshape(-1).contiguous()
         B = idx.shape[0]
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -77,6 +91,8 @@ class SequenceWindows:
                       "fcr_window_gather")
         if check and int(self._bad.item()):
             raise IndexError(f"{int(self._bad.item())} index(es) outside [0, {len(self)})")
+        if preview is not None:
+            return x, y, z, reference_preview(self.X, idx, self.traj_len, preview)
         return x, y, z
 
     def __getitem__(self, i):
@@ -87,11 +103,14 @@ class SequenceWindows:
 class DeviceLoader:
     """DataLoader(windows or Subset(windows, indices), batch_size, shuffle) yielding device batches.
 
-    ``indices`` plays torch.utils.data.Subset (UL/Main.py:282-291 resamples every N-th sample)."""
+    ``indices`` plays torch.utils.data.Subset (UL/Main.py:282-291 resamples every N-th sample). ``preview=N``: every
+    batch is ``(x, y, z, ref_h (B,N))`` (:meth:`SequenceWindows.gather`), which the training loops hand to the loss as
+    ``ref_horizon``."""
 
     def __init__(self, windows: SequenceWindows, batch_size: int, shuffle: bool = False, indices=None,
-                 generator: torch.Generator | None = None, check: bool = False):
+                 generator: torch.Generator | None = None, check: bool = False, preview: int | None = None):
         self.w, self.batch_size, self.shuffle, self.check = windows, int(batch_size), bool(shuffle), check
+        self.preview = None if preview is None else int(preview)
         base = torch.arange(len(windows)) if indices is None else torch.as_tensor(indices, dtype=torch.int64)
         self.indices = base.to(windows.device)
         self.generator = generator
@@ -105,4 +124,4 @@ class DeviceLoader:
             perm = torch.randperm(order.numel(), generator=self.generator).to(order.device)
             order = order[perm]
         for s in range(0, order.numel(), self.batch_size):
-            yield self.w.gather(order[s:s + self.batch_size], check=self.check)
+            yield self.w.gather(order[s:s + self.batch_size], check=self.check, preview=self.preview)

@@ -125,11 +125,20 @@ class MPCLoss(nn.Module):
     ``self.last_call`` (a :class:`~.rollout.CallInfo`) reports the kernel families the last call's passes launched
     and its workspace. ``many_min_models``: the least M at which :meth:`forward_many` runs the many-model kernels
     (None: :data:`.many.MANY_MIN_MODELS`, the measured crossover).
+
+    ``terms`` (a :class:`~.loss_terms.LossTerms`; for :meth:`forward_many` also a sequence of M of them, one per bank
+    model): the pressure bounds, the constraint's weight and, when its ``alpha`` is set, the command weight in place of
+    ``alpha``. None is the reference's loss; ``LossTerms()`` gives the same bits. ``forward(..., ref_horizon=)``: a
+    ``(B, N)`` per-step reference r_j (``(M, B, N)`` for :meth:`forward_many`) for the error of step j and the
+    controller call that produces u_j; None holds ``X[:, 2]`` over the horizon. It is a plain input: no gradient.
     """
 
     def __init__(self, prediction_horizon=10, alpha=0.1, precision="fp32", small_batch_limit=None,
-                 wide_keep_budget=None, many_min_models=None):
+                 wide_keep_budget=None, many_min_models=None, terms=None):
         super().__init__()
+        from .loss_terms import resolve
+        self.terms = resolve(terms)
+        self._tables = {}              # device -> ((rows), table tensor): the bank's rows on the device, built once
         self.N = prediction_horizon
         self.alpha = alpha
         self.precision = precision     # "fp32" (reference-accurate) or "f16" (config 3, include/fcr.h)
@@ -142,14 +151,22 @@ class MPCLoss(nn.Module):
 
     def forward(self, simulator: nn.Module, controller: nn.Module, input_controller: torch.Tensor,
                 output_controller: torch.Tensor, states: torch.Tensor, device: torch.device,
-                enable_noise=False, noise: torch.Tensor | None = None):
+                enable_noise=False, noise: torch.Tensor | None = None, ref_horizon: torch.Tensor | None = None,
+                _terms=None):
         X = input_controller
         dev = torch.device(device)
         if dev.type != X.device.type or (dev.index is not None and dev.index != X.device.index):
             raise RuntimeError(f"MPCLoss: inputs are on {X.device}, device argument is {device}")
         B = X.shape[0]
+        terms = _terms if _terms is not None else self.terms   # (_terms: forward_many's loop route, model m's own)
+        if terms is not None and not hasattr(terms, "as_row"):
+            raise ValueError("MPCLoss.forward: a sequence of LossTerms is for forward_many (one per bank model)")
+        row = None if terms is None else terms.as_row(self.alpha)
+        if ref_horizon is not None and tuple(ref_horizon.shape) != (B, self.N):
+            raise ValueError(f"ref_horizon must be (B, N) = {(B, self.N)}, got {tuple(ref_horizon.shape)}")
         if X.device.type == "cpu":
-            return self._forward_host(simulator, controller, X, output_controller, states, device, enable_noise, noise)
+            return self._forward_host(simulator, controller, X, output_controller, states, device, enable_noise, noise,
+                                      row, ref_horizon)
         if enable_noise and noise is None:
             noise = torch.stack([torch.randn(B, 4, device=X.device) * 0.01 for _ in range(self.N)], dim=1)
         elif not enable_noise:
@@ -159,13 +176,13 @@ class MPCLoss(nn.Module):
         self.last_call = CallInfo(_native.make_options(self.small_batch_limit, self.wide_keep_budget))
         loss, cost, command, error, prediction, xhat = rollout(
             X, output_controller, states, _controller_params(controller), _simulator_params(simulator),
-            self.N, self.alpha, noise, self.precision, self.last_call)
+            self.N, self.alpha, noise, self.precision, self.last_call, row, ref_horizon)
         self.last_trajectory = xhat
         return loss, {"loss": cost, "command": command, "error": error, "prediction": prediction}
 
     def forward_many(self, simulator: nn.Module, bank: nn.Module, input_controller: torch.Tensor,
                      output_controller: torch.Tensor, states: torch.Tensor, device: torch.device,
-                     enable_noise=False, noise: torch.Tensor | None = None):
+                     enable_noise=False, noise: torch.Tensor | None = None, ref_horizon: torch.Tensor | None = None):
         """:meth:`forward` for the M controllers of a :class:`~.many.ControllerBank` against one shared simulator, on
         inputs stacked model-major: ``X (M,B,3)``, ``u0 (M,B,1)``, ``states (M,B,10,5)``, ``noise (M,B,N,4)`` or None.
         Returns ``(losses (M,), features)`` with ``loss`` / ``command`` / ``error`` as ``(M,B)`` and ``prediction`` as
@@ -179,20 +196,42 @@ class MPCLoss(nn.Module):
         ``M >= many_min_models`` each pass is ONE launch of the many-model kernels (a workgroup per 16-trajectory group
         of one model); anything else — CPU tensors, H > 52, f16, a large B — loops over the models through
         :meth:`forward`, with the same results. ``self.last_call`` (a :class:`~.many.ManyCallInfo`) says which route
-        ran (``route``: "many" or "loop", and ``why``)."""
+        ran (``route``: "many" or "loop", and ``why``). With ``terms`` a sequence of M :class:`~.loss_terms.LossTerms`
+        model m runs under its own row (alpha, bounds, weight) on either route — an alpha / weight / bound sweep in one
+        launch; ``ref_horizon`` is ``(M,B,N)``."""
         from .many import forward_many
         return forward_many(self, simulator, bank, input_controller, output_controller, states, device, enable_noise,
-                            noise)
+                            noise, ref_horizon)
 
-    def _forward_host(self, simulator, controller, X, u0, states, device, enable_noise, noise):
+    def terms_table(self, n_models, device):
+        """The bank's rows (``LossTerms.as_row``) as an ``(M, 6)`` float32 tensor on ``device`` — ``(1, 6)`` when one
+        LossTerms is shared by every model — cached per device; None without terms."""
+        from .loss_terms import resolve
+        terms = resolve(self.terms, n_models if not hasattr(self.terms, "as_row") else None)
+        if terms is None:
+            return None
+        rows = tuple(t.as_row(self.alpha) for t in ((terms,) if hasattr(terms, "as_row") else terms))
+        key = str(torch.device(device))
+        hit = self._tables.get(key)
+        if hit is None or hit[0] != rows:
+            hit = (rows, torch.tensor(rows, dtype=torch.float32, device=device))
+            self._tables[key] = hit
+        return hit[1]
+
+    def _forward_host(self, simulator, controller, X, u0, states, device, enable_noise, noise, row=None, ref_h=None):
         """The rollout where the reference runs it without a GPU (``device = cpu``, UL/Main.py:38): its op
         sequence (Functions.py:1386-1472) on the caller's own modules — ``simulator(window, device)`` and
         ``controller(x)`` are LSTMModel's / FNNModel's torch layers off-device — under autograd, so
         ``loss.backward()`` reaches the controller parameters and ``output_controller`` as the reference's
         does (the frozen LSTM's weight gradients included). Noise: ``randn_like(x̂) * 0.01`` drawn after every
-        surrogate call in the reference's order (:1400-1402, :1438-1440), or the given (B, N, 4) ``noise``."""
+        surrogate call in the reference's order (:1400-1402, :1438-1440), or the given (B, N, 4) ``noise``. ``row``:
+        the terms (``LossTerms.as_row``; None = the reference's literals); ``ref_h`` (B, N): r_j for the error of step
+        j and the controller call producing u_j (None: ``X[:, -1]`` throughout), detached."""
         N, alpha, relu = self.N, self.alpha, self.activation
         B = X.shape[0]
+        p1_lo, p1_hi, p2_lo, p2_hi, w_con = 0.0, 2.122366, 0.0, 1.036233, 1.0
+        if row is not None:
+            alpha, p1_lo, p1_hi, p2_lo, p2_hi, w_con = row
 
         def perturb(xh, j):
             if noise is not None and enable_noise:
@@ -202,9 +241,15 @@ class MPCLoss(nn.Module):
             return xh
 
         def constraint(xh):                                                       # Functions.py:1411, 1449
-            return relu(-xh[:, 1]) + relu(-xh[:, 2]) + relu(xh[:, 1] - 2.122366) + relu(xh[:, 2] - 1.036233)
+            if row is None:
+                return relu(-xh[:, 1]) + relu(-xh[:, 2]) + relu(xh[:, 1] - 2.122366) + relu(xh[:, 2] - 1.036233)
+            return w_con * (relu(p1_lo - xh[:, 1]) + relu(p2_lo - xh[:, 2]) + relu(xh[:, 1] - p1_hi)
+                            + relu(xh[:, 2] - p2_hi))
 
-        ref = X[:, -1]                                                            # :1392
+        if ref_h is not None:
+            ref_h = ref_h.detach().to(X.dtype)
+        r = (lambda j: X[:, -1]) if ref_h is None else (lambda j: ref_h[:, j])    # :1392
+        ref = r(0)
         window = states.clone()                                                   # :1395-1396
         window[:, -1, -1] = u0.reshape(B)
         xh = perturb(simulator(window, device), 0)                                # :1399-1402
@@ -215,6 +260,7 @@ class MPCLoss(nn.Module):
         preds, traj = [u_next], [xh]
         for j in range(N - 1):                                                    # :1421
             u_prev = u_next
+            ref = r(j + 1)
             u_next = controller(torch.stack((xh[:, 0], xh[:, 3], ref), dim=1))    # :1424-1430
             window = torch.cat((window[:, 1:10, :], torch.cat((xh, u_next), dim=1).unsqueeze(1)), dim=1)   # :1433-1434
             xh = perturb(simulator(window, device), j + 1)                        # :1437-1440
@@ -238,7 +284,9 @@ class NeuralNetwork:
     def captured_step(simulator, model, loss_function, optimizer, device, enable_noise=False, grad_sync=None,
                       warmup=2):
         """The body of :meth:`train_model`'s batch loop as a :class:`~.graphed.CapturedStep` (one HIP graph
-        replay per batch; pass it as ``train_model(..., step=...)``, reusable across epochs)."""
+        replay per batch; pass it as ``train_model(..., step=...)``, reusable across epochs). The loss's ``terms`` are
+        constants of the graph (change them and capture a new step). A loader with a reference preview (a fourth batch
+        element) is not replayed from a graph: ``train_model(..., step=...)`` raises ``NotImplementedError`` for it."""
         from .graphed import CapturedStep
 
         def body(X, z):
@@ -264,8 +312,9 @@ class NeuralNetwork:
         total = 0.0
         feats = {"loss": [], "command": [], "error": [], "prediction": []}
         n_batches = 0
-        for X, _, z in data_loader:
+        for X, _, z, *more in data_loader:
             X, z = X.to(device), z.to(device)
+            ref_h = more[0].to(device) if more else None   # (X, y, z, ref_h): the reference over the horizon
             optimizer.zero_grad()
             if X.shape[0] == 0:
                 # an empty shard (more ranks than trajectories in a short last batch): no rollout, but the
@@ -275,7 +324,10 @@ class NeuralNetwork:
                     optimizer.step()
                 continue
             output = model(X)
-            loss, f = loss_function(simulator, model, X, output, z, device, enable_noise)
+            if ref_h is None:
+                loss, f = loss_function(simulator, model, X, output, z, device, enable_noise)
+            else:
+                loss, f = loss_function(simulator, model, X, output, z, device, enable_noise, ref_horizon=ref_h)
             for k in feats:
                 feats[k].append(f[k])
             loss.backward()
@@ -317,7 +369,10 @@ class NeuralNetwork:
         feats = {k: [] for k in keys}
         total = None
         n_batches = 0
-        for X, _, z in data_loader:
+        for X, _, z, *more in data_loader:
+            if more:
+                raise NotImplementedError("train_model(step=...): a loader with a reference preview (a fourth batch "
+                                          "element) is not replayed from a graph; train it without step / graphed")
             X, z = X.to(device), z.to(device)
             if X.shape[0] == 0:   # an empty shard: join the all-reduce and step, as the eager loop does
                 step.skip_empty(X, z)
@@ -337,7 +392,7 @@ class NeuralNetwork:
         total = 0.0
         n = 0
         with torch.no_grad():
-            for X, y, _ in data_loader:
+            for X, y, *_ in data_loader:
                 X, y = X.to(device), y.to(device)
                 total += loss_function(model(X), y).item()
                 n += 1
@@ -352,7 +407,7 @@ class NeuralNetwork:
         dev = next(model.parameters()).device
         preds = []
         with torch.no_grad():
-            for X, _, _ in data_loader:
+            for X, *_ in data_loader:
                 preds.append(model(X.to(dev)))
         return torch.cat(preds, dim=0)
 

@@ -184,12 +184,13 @@ class ManyCallInfo:
 
 class ManyRolloutFn(torch.autograd.Function):
     """RolloutFn for M stacked models. Inputs: X (M,B,3), u0 (M,B,1), states (M,B,10,5), noise (M,B,N,4) or None, the
-    bank's (M,hidden,3), (M,hidden), (M,hidden), the LSTM weights, N, alpha, the small-batch limit, a ManyCallInfo.
+    bank's (M,hidden,3), (M,hidden), (M,hidden), the LSTM weights, N, alpha, the small-batch limit, a ManyCallInfo; then,
+    optionally, the table of the models' terms ((M,6) or, shared, (1,6) float32 on the device) and ref_h (M,B,N).
     Outputs: loss (M,), cost / command / error (M,B), prediction (M,B*N), xhat (M,B,N,4)."""
 
     @staticmethod
     def forward(ctx, X, u0, states, noise, W_inp, b_inp, W_out, w_ih0, w_ih1, w_ih2, w_hh0, w_hh1, w_hh2, fc_w, fc_b,
-                N, alpha, small_limit, info):
+                N, alpha, small_limit, info, table=None, ref_h=None):
         lib = _native.load()
         dev = X.device
         M, B = X.shape[0], X.shape[1]
@@ -211,25 +212,44 @@ class ManyRolloutFn(torch.autograd.Function):
         w.fc_w, w.fc_b = keep[9].data_ptr(), keep[10].data_ptr()
         Xc, u0c, stc = X.contiguous(), u0.contiguous(), states.contiguous()
         nzc = noise.contiguous() if noise is not None else None
-        _native.check(lib.fcr_forward_many(ctypes.byref(dims), ctypes.byref(opts), M, ctypes.byref(w), _ptr(Xc), _ptr(u0c),
-                                           _ptr(stc), _ptr(nzc), _ptr(loss), _ptr(cost), _ptr(command), _ptr(error),
-                                           _ptr(prediction), _ptr(xhat), int(need_grad), _ptr(ws), ws.numel(),
-                                           _stream(dev)), "fcr_forward_many")
+        terms = None
+        if table is not None or ref_h is not None:
+            rhc = ref_h.contiguous() if ref_h is not None else None
+            terms = (table, rhc)
+            ft = ManyRolloutFn._terms(terms, alpha, B, N)
+            _native.check(lib.fcr_forward_many_terms(ctypes.byref(dims), ctypes.byref(opts), M, ctypes.byref(w),
+                                                     ctypes.byref(ft), _ptr(Xc), _ptr(u0c), _ptr(stc), _ptr(nzc), _ptr(loss),
+                                                     _ptr(cost), _ptr(command), _ptr(error), _ptr(prediction), _ptr(xhat),
+                                                     int(need_grad), _ptr(ws), ws.numel(), _stream(dev)),
+                          "fcr_forward_many_terms")
+        else:
+            _native.check(lib.fcr_forward_many(ctypes.byref(dims), ctypes.byref(opts), M, ctypes.byref(w), _ptr(Xc),
+                                               _ptr(u0c), _ptr(stc), _ptr(nzc), _ptr(loss), _ptr(cost), _ptr(command),
+                                               _ptr(error), _ptr(prediction), _ptr(xhat), int(need_grad), _ptr(ws),
+                                               ws.numel(), _stream(dev)), "fcr_forward_many")
         info.forward, info.backward = _native.KERNEL_FAMILIES[opts.kernels], None
         info.workspace_bytes = ws.numel()
         ctx.mark_non_differentiable(cost, command, error, prediction, xhat)
         ctx.set_materialize_grads(False)
         if need_grad:
             ctx.ws, ctx.dims, ctx.info, ctx.small_limit, ctx.M = ws, dims, info, int(small_limit), M
+            ctx.terms, ctx.alpha = terms, alpha
             ctx.save_for_backward(Xc, stc, prediction)
             ctx.ctrl_shapes = (W_inp.shape, b_inp.shape, W_out.shape)
         return loss, cost, command, error, prediction, xhat
 
     @staticmethod
+    def _terms(terms, alpha, B, N):
+        """fcr_loss_terms of a many call: the table's row stride is 0 for one shared row; ref_h is (M,B,N)."""
+        table, ref_h = terms
+        return _native.make_loss_terms(_native.default_terms_row(alpha), ref_h, (B * N, N, 1), table,
+                                       0 if table is None or table.shape[0] == 1 else table.stride(0))
+
+    @staticmethod
     def backward(ctx, g_loss, *unused):
         if g_loss is None:
             ctx.ws = None
-            return (None,) * 19
+            return (None,) * 21
         if ctx.ws is None:
             raise RuntimeError("MPCLoss.forward_many: trying to backward through the same rollout a second time; its "
                                "workspace was released by the first backward: recompute the losses")
@@ -242,12 +262,19 @@ class ManyRolloutFn(torch.autograd.Function):
         g_wi, g_bi, g_wo = (torch.empty(s, **f32) for s in ctx.ctrl_shapes)
         dl = g_loss.detach().to(torch.float32).reshape(M).contiguous()
         opts = _native.FcrOptions(ctx.small_limit, 0, _native.OPT_INHERIT)
-        _native.check(lib.fcr_backward_many(ctypes.byref(ctx.dims), ctypes.byref(opts), M, _ptr(Xc), _ptr(stc),
-                                            _ptr(prediction), _ptr(dl), _ptr(g_u0), _ptr(g_wi), _ptr(g_bi), _ptr(g_wo),
-                                            _ptr(ctx.ws), ctx.ws.numel(), _stream(dev)), "fcr_backward_many")
+        if ctx.terms is not None:
+            ft = ManyRolloutFn._terms(ctx.terms, ctx.alpha, B, ctx.dims.N)
+            _native.check(lib.fcr_backward_many_terms(ctypes.byref(ctx.dims), ctypes.byref(opts), M, ctypes.byref(ft),
+                                                      _ptr(Xc), _ptr(stc), _ptr(prediction), _ptr(dl), _ptr(g_u0), _ptr(g_wi),
+                                                      _ptr(g_bi), _ptr(g_wo), _ptr(ctx.ws), ctx.ws.numel(), _stream(dev)),
+                          "fcr_backward_many_terms")
+        else:
+            _native.check(lib.fcr_backward_many(ctypes.byref(ctx.dims), ctypes.byref(opts), M, _ptr(Xc), _ptr(stc),
+                                                _ptr(prediction), _ptr(dl), _ptr(g_u0), _ptr(g_wi), _ptr(g_bi), _ptr(g_wo),
+                                                _ptr(ctx.ws), ctx.ws.numel(), _stream(dev)), "fcr_backward_many")
         ctx.info.backward = _native.KERNEL_FAMILIES[opts.kernels]
         ctx.ws = None
-        return (None, g_u0, None, None, g_wi, g_bi, g_wo) + (None,) * 12
+        return (None, g_u0, None, None, g_wi, g_bi, g_wo) + (None,) * 14
 
 
 def _loop_reason(loss_fn, simulator, bank, X):
@@ -270,9 +297,10 @@ def _loop_reason(loss_fn, simulator, bank, X):
     return None
 
 
-def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=False, noise=None):
+def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=False, noise=None, ref_horizon=None):
     """:meth:`MPCLoss.forward_many` (see there)."""
     from .functions import _simulator_params
+    from .loss_terms import resolve
     dev = torch.device(device)
     if dev.type != X.device.type or (dev.index is not None and dev.index != X.device.index):
         raise RuntimeError(f"MPCLoss: inputs are on {X.device}, device argument is {device}")
@@ -285,6 +313,11 @@ def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=F
                          f"{tuple(states.shape)}")
     if noise is not None and tuple(noise.shape) != (M, B, N, 4):
         raise ValueError(f"forward_many: noise must be (M,B,N,4) = {(M, B, N, 4)}, got {tuple(noise.shape)}")
+    if ref_horizon is not None and tuple(ref_horizon.shape) != (M, B, N):
+        raise ValueError(f"forward_many: ref_horizon must be (M,B,N) = {(M, B, N)}, got {tuple(ref_horizon.shape)}")
+    terms = loss_fn.terms
+    if terms is not None and not hasattr(terms, "as_row"):
+        terms = resolve(terms, M)   # one LossTerms per model
     u0 = u0.reshape(M, B, 1)
     why = _loop_reason(loss_fn, simulator, bank, X)
     if why is not None:
@@ -293,7 +326,9 @@ def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=F
         losses, feats, traj = [], [], []
         for m in range(M):
             l, f = loss_fn.forward(simulator, bank.member(m), X[m], u0[m], states[m], device, enable_noise,
-                                   None if noise is None else noise[m])
+                                   None if noise is None else noise[m],
+                                   None if ref_horizon is None else ref_horizon[m],
+                                   terms[m] if isinstance(terms, tuple) else None)
             losses.append(l)
             feats.append(f)
             traj.append(loss_fn.last_trajectory)
@@ -308,7 +343,10 @@ def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=F
     elif not enable_noise:
         noise = None
     w_ih, w_hh, fc_w, fc_b = _simulator_params(simulator)
-    for t in [u0, states, bank.w_inp] + list(w_ih) + list(w_hh) + [fc_w, fc_b] + ([] if noise is None else [noise]):
+    if ref_horizon is not None:
+        ref_horizon = _dev_f32(ref_horizon.detach(), "ref_horizon")
+    for t in ([u0, states, bank.w_inp] + list(w_ih) + list(w_hh) + [fc_w, fc_b] + ([] if noise is None else [noise])
+              + ([] if ref_horizon is None else [ref_horizon])):
         if t.device != X.device:
             raise RuntimeError(f"all rollout tensors must be on {X.device}, found one on {t.device}")
     limit = loss_fn.small_batch_limit if loss_fn.small_batch_limit is not None else _native.small_batch_limit()
@@ -317,7 +355,7 @@ def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=F
         _dev_f32(X, "X"), _dev_f32(u0, "u0"), _dev_f32(states, "states"),
         None if noise is None else _dev_f32(noise, "noise"), bank.w_inp, bank.b_inp, bank.w_out,
         *[_dev_f32(t, "lstm weight") for t in list(w_ih) + list(w_hh) + [fc_w, fc_b]], int(N), float(loss_fn.alpha),
-        int(limit), info)
+        int(limit), info, loss_fn.terms_table(M, X.device), ref_horizon)
     loss_fn.last_trajectory = xhat
     loss_fn.last_call = info
     return loss, {"loss": cost, "command": command, "error": error, "prediction": prediction}
@@ -325,7 +363,8 @@ def forward_many(loss_fn, simulator, bank, X, u0, states, device, enable_noise=F
 
 def zip_loaders(loaders):
     """M loaders (``DataLoader`` or :class:`~.data.DeviceLoader`, one per model, each with its own shuffling) as one
-    iterable of stacked batches ``(X (M,B,3), y (M,B,...), states (M,B,10,5))``. Refuses loaders whose batch sizes
+    iterable of stacked batches ``(X (M,B,3), y (M,B,...), states (M,B,10,5))`` — and ``ref_h (M,B,N)`` when the loaders
+    yield a fourth element (a reference preview). Refuses loaders whose batch sizes
     differ within a step, or that run out at different steps: every model of a bank has the same B."""
     loaders = list(loaders)
     if not loaders:
@@ -347,7 +386,10 @@ def zip_loaders(loaders):
         sizes = [b[0].shape[0] for b in batches]
         if len(set(sizes)) != 1:
             raise ValueError(f"zip_loaders: step {step}: batch sizes differ between the models: {sizes}")
-        yield tuple(torch.stack([b[k] for b in batches], dim=0) for k in range(3))
+        width = {len(b) for b in batches}
+        if len(width) != 1 or width.pop() not in (3, 4):
+            raise ValueError(f"zip_loaders: step {step}: batches must all be (X, y, z) or all (X, y, z, ref_h)")
+        yield tuple(torch.stack([b[k] for b in batches], dim=0) for k in range(len(batches[0])))
         step += 1
 
 
@@ -373,16 +415,20 @@ def train_models(batches, simulator, bank, loss_function, optimizer, device, ena
     bank.train()
     feats = {k: [] for k in FEATURE_KEYS}
     total, n_batches = None, 0
-    for X, _, z in batches:
+    for X, _, z, *more in batches:
         X, z = X.to(device), z.to(device)
+        ref_h = more[0].to(device) if more else None   # (X, y, z, ref_h): the reference over the horizon, (M,B,N)
         if step is not None:
+            if ref_h is not None:
+                raise NotImplementedError("train_models(step=...): batches with a reference preview (a fourth element) "
+                                          "are not replayed from a graph; train them without step")
             losses, *f = step(X, z)
             f = dict(zip(FEATURE_KEYS, (v.clone() for v in f)))
             losses = losses.clone()
         else:
             optimizer.zero_grad()
             output = bank(X)
-            losses, f = loss_function.forward_many(simulator, bank, X, output, z, device, enable_noise)
+            losses, f = loss_function.forward_many(simulator, bank, X, output, z, device, enable_noise, None, ref_h)
             losses.sum().backward()   # the models are independent: d sum / d (model m's parameters) = d losses[m] / d them
             optimizer.step()
             losses = losses.detach()

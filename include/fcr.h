@@ -202,6 +202,60 @@ int fcr_fnn_backward_many(int32_t n_models, int32_t B, int32_t in_dim, int32_t h
                           float *g_w_inp, float *g_b_inp, float *g_w_out, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * The loss's terms as data. A pure addition to ABI v8 (no existing call or struct changed): look the symbols up.
+ * For trajectory b, horizon step j = 0 .. N-1 and the scaled prediction xhat_j = (y_dot, p1, p2, z):
+ *   err_j = (xhat_j[0] - r_j)^2
+ *   con_j = w_con * (relu(p1_lo - p1) + relu(p2_lo - p2) + relu(p1 - p1_hi) + relu(p2 - p2_hi))
+ *   tot  += (err_j + alpha * du_j^2) + con_j ;   u_{j+1} = controller(xhat_j[0], xhat_j[3], r_{j+1})
+ * fcr_loss_terms_default() gives the reference's loss (Functions.py:1405-1452): p*_lo = 0, p1_hi = 2.122366,
+ * p2_hi = 1.036233 (32e6 Pa over the shipped output scaler's max_abs_), w_con = 1, r_j = X[b, 2] at every j; with it
+ * (and alpha = dims->alpha) the *_terms calls return the bits of the calls without terms, which are exactly that.
+ *   alpha                     replaces dims->alpha, which the *_terms calls IGNORE
+ *   p1_lo .. p2_hi, w_con     in the surrogate's scaled units. A bound may be -inf (lo) / +inf (hi): switched off.
+ *                             Refused (FCR_EINVAL, before any launch): a NaN, lo > hi, w_con < 0, a non-finite alpha
+ *   ref, ref_stride_b/_j      DEVICE floats, r_j of trajectory b = ref[b * ref_stride_b + j * ref_stride_j]; a (B,N)
+ *                             array passes (N, 1). NULL = X's column 2 (strides ignored). A plain input: no gradient.
+ *                             The backward must be given the forward's terms.
+ * The many-model calls only:
+ *   table, table_stride       DEVICE floats, model m's six scalars {alpha, p1_lo, p1_hi, p2_lo, p2_hi, w_con} at
+ *                             table + m * table_stride (stride 0: one row shared by every model); NULL = the struct's
+ *                             own scalars for every model. The table's VALUES are the caller's to check (the library
+ *                             does not read device memory on the host); with a table the struct's scalars are unused.
+ *   ref_stride_m              model m's references start at ref + m * ref_stride_m: an (M,B,N) array passes
+ *                             (B N, N, 1).
+ * Workspace sizes are those of the calls without terms.
+ */
+typedef struct fcr_loss_terms {
+    float alpha, p1_lo, p1_hi, p2_lo, p2_hi, w_con;
+    const float *ref;
+    int64_t ref_stride_b, ref_stride_j;
+    const float *table;
+    int64_t table_stride, ref_stride_m;
+} fcr_loss_terms;
+void fcr_loss_terms_default(fcr_loss_terms *terms, float alpha);
+int fcr_forward_terms(const fcr_dims *dims, fcr_options *opts, const fcr_weights *w, const fcr_loss_terms *terms,
+                      const float *X, const float *u0, const float *states, const float *noise,
+                      float *loss, float *cost, float *command, float *error,
+                      float *prediction, float *xhat,
+                      int with_backward, void *ws, size_t ws_bytes, void *stream);
+int fcr_backward_terms(const fcr_dims *dims, fcr_options *opts, const fcr_loss_terms *terms,
+                       const float *X, const float *states, const float *prediction,
+                       const float *dloss,
+                       float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out,
+                       void *ws, size_t ws_bytes, void *stream);
+int fcr_forward_many_terms(const fcr_dims *dims, fcr_options *opts, int32_t n_models, const fcr_weights *w,
+                           const fcr_loss_terms *terms,
+                           const float *X, const float *u0, const float *states, const float *noise,
+                           float *loss, float *cost, float *command, float *error,
+                           float *prediction, float *xhat,
+                           int with_backward, void *ws, size_t ws_bytes, void *stream);
+int fcr_backward_many_terms(const fcr_dims *dims, fcr_options *opts, int32_t n_models, const fcr_loss_terms *terms,
+                            const float *X, const float *states, const float *prediction,
+                            const float *dloss,
+                            float *g_u0, float *g_w_inp, float *g_b_inp, float *g_w_out,
+                            void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Batched forging-press plant: the state update x_{t+1} = F(x_t, u_t) of
  * FeasibilityRecovery.Ruge_Kuta (Functions.py:1743-1781) over the dynamics of forging_model
  * (Functions.py:1615-1740; smooth = 1: template_model.py:19-149, pressures floored by smooth_relu),
