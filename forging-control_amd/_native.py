@@ -36,7 +36,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_forward_many", "fcr_backward_many", "fcr_fnn_forward_many", "fcr_fnn_backward_many",
            "fcr_closed_loop_run_bank", "fcr_press_nominal", "fcr_plant_rk4_press", "fcr_feasibility_project_press",
            "fcr_closed_loop_run_bank_press", "fcr_loss_terms_default", "fcr_forward_terms", "fcr_backward_terms",
-           "fcr_forward_many_terms", "fcr_backward_many_terms")
+           "fcr_forward_many_terms", "fcr_backward_many_terms", "fcr_plant_rk4_vjp", "fcr_closed_loop_vjp_workspace_size",
+           "fcr_closed_loop_vjp")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -154,6 +155,22 @@ class FcrPress(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in (
         "m_mass", "b_damp", "ft", "d1", "d2", "g", "kb", "v1_0", "v2_0", "kl_1", "kl_2", "cd", "rho", "d", "ps", "pt",
         "mu", "k", "w0", "h0", "b0", "t_def", "t1", "m0", "m1", "m2", "m3", "m4")]
+
+
+class FcrClosedLoopGrad(ctypes.Structure):
+    """fcr_closed_loop_grad (include/fcr.h): the closed loop's stored run and incoming gradients, and where its
+    vector-Jacobian product goes."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("ts", ctypes.c_double),
+        ("substeps", ctypes.c_int32), ("smooth", ctypes.c_int32), ("ref", ctypes.c_void_p),
+        ("ctrl_w_inp", ctypes.c_void_p), ("ctrl_b_inp", ctypes.c_void_p), ("ctrl_w_out", ctypes.c_void_p),
+        ("ctrl_hidden", ctypes.c_int32), ("in_scale", ctypes.c_double * 2),
+        ("ref_scale", ctypes.c_double), ("out_scale", ctypes.c_double),
+        ("x", ctypes.c_void_p), ("u", ctypes.c_void_p), ("g_x", ctypes.c_void_p), ("g_u", ctypes.c_void_p),
+        ("press", ctypes.c_void_p), ("stride_traj", ctypes.c_int64),
+        ("g_x0", ctypes.c_void_p), ("dv", ctypes.c_void_p),
+        ("g_w_inp", ctypes.c_void_p), ("g_b_inp", ctypes.c_void_p), ("g_w_out", ctypes.c_void_p),   # fp64
+    ]
 
 
 class FcrSupervised(ctypes.Structure):
@@ -274,6 +291,15 @@ def load() -> ctypes.CDLL:
             lib.fcr_backward_many_terms.argtypes = [ctypes.POINTER(FcrDims), po, i32, pt, vp, vp, vp, vp, vp, vp, vp, vp,
                                                     vp, sz, vp]
             lib.fcr_backward_many_terms.restype = i32
+        # the differentiable press (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the
+        # addition loads without it; a backward through the press then raises AttributeError.
+        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_plant_rk4_vjp"):
+            lib.fcr_plant_rk4_vjp.argtypes = [i32, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp]
+            lib.fcr_plant_rk4_vjp.restype = i32
+            lib.fcr_closed_loop_vjp_workspace_size.argtypes = [i32, i32, i32, ctypes.POINTER(sz)]
+            lib.fcr_closed_loop_vjp_workspace_size.restype = i32
+            lib.fcr_closed_loop_vjp.argtypes = [ctypes.POINTER(FcrClosedLoopGrad), vp, sz, vp]
+            lib.fcr_closed_loop_vjp.restype = i32
         lib.fcr_fnn_forward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         lib.fcr_fnn_forward_many.restype = i32
         lib.fcr_fnn_backward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]

@@ -151,7 +151,8 @@ class ClosedLoop:
         self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
-            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, plant_params=None):
+            meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, plant_params=None,
+            differentiable: bool = False):
         """``process_noise`` / ``meas_noise``: (B,T,5) pre-drawn ``w0`` / ``v0`` (:func:`harness_noise`), or None.
         ``w`` is in the units of x_dot and is held over the step: every RK4 stage evaluates f(x,u) + w[b,t].
         ``x[:,t+1]`` records x_{t+1} + v[b,t]; the controller reads that record, the press integrates on from the
@@ -167,9 +168,30 @@ class ClosedLoop:
         ``plant_params``: the press the loop steps — a :class:`~.plant.PressParams` or ``(28,)`` row for all
         trajectories, or a ``(B,28)`` table, one row per trajectory; ``None``: the constructor's, by default the
         reference's press. With parameters (here or as the ``feasibility``'s ``model_params``) the call runs the bank's
-        kernels with one model (:class:`ClosedLoopBank`), whose trajectories are this loop's bit for bit."""
+        kernels with one model (:class:`ClosedLoopBank`), whose trajectories are this loop's bit for bit.
+
+        ``differentiable=True``: ``(x, u)`` are attached to the graph of the controller's three parameters and of ``x0``
+        (under ``torch.no_grad()`` they come back detached). The forward is the launch above, ``x`` and ``u`` bit-equal to
+        ``differentiable=False``; the backward is the adjoint of the loop (``fcr_closed_loop_vjp``, csrc/fcr_press_grad.h;
+        DESIGN.md §7.13) on the stored ``x, u``, with ``plant_params`` in every form above; gradients reach the parameters
+        in their own dtype, summed in fp64 in a fixed order (two backward calls give the same bits). The fp32 controller
+        chain is recomputed in the forward's operation order, so its ReLU masks (ReLU'(0) = 0) and Hardtanh mask (1 only
+        for ``-1 < v < 1``) are the forward's own; float casts count as the identity. The press's conventions where its
+        derivative is singular are :func:`~.plant.forging_rk4`'s: deformation force differentiated only where ``y > 0``
+        and ``y_dot > 0``; valve-flow derivatives 0 at a zero pressure difference, branch by ``z >= 0``; friction slope
+        ``FT/0.5`` where ``|y_dot| <= 0.5``, else 0; smooth floor ``0.5 (1 + p / sqrt(p^2 + eps))``. Raises ``ValueError``
+        with ``process_noise``, ``meas_noise`` (the record ``x + v`` does not give the unperturbed state back exactly) or
+        ``feasibility`` (the projection is not differentiable). No gradient reaches ``ref`` or ``plant_params``.
+        Gradients through the press grow with T: back-propagation through hundreds of steps is the caller's risk."""
         if plant_params is None:
             plant_params = self.plant_params
+        if differentiable:
+            for name, given in (("process_noise", process_noise), ("meas_noise", meas_noise), ("feasibility", feasibility)):
+                if given is not None:
+                    raise ValueError(f"ClosedLoop.run(differentiable=True) does not take {name}: the adjoint covers the "
+                                     "noise-free loop without recovery (DESIGN.md §7.13)")
+            if torch.is_grad_enabled():
+                return _ClosedLoopGrad.apply(self, x0, ref, plant_params, *_controller_params(self.controller))
         if plant_params is not None or (feasibility is not None and feasibility.model_params is not None):
             if x0.dim() != 2 or ref.dim() != 2:
                 raise ValueError(f"x0 must be (B,5) and ref (B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
@@ -243,6 +265,73 @@ class ClosedLoop:
         track = _shadow_track(x[:, 0, 1:5], u, simulator, s_in, s_out, lstm_noise)
         results_lstm = {"y_dot": track[:, :, 0], "p1": track[:, :, 1], "p2": track[:, :, 2], "z": track[:, :, 3]}
         return results, results_lstm
+
+
+class _ClosedLoopGrad(torch.autograd.Function):
+    """:meth:`ClosedLoop.run` attached to the graph: the forward is the plain launch (which reads the controller's
+    parameters itself), the backward ``fcr_closed_loop_vjp`` on the stored run."""
+
+    @staticmethod
+    def forward(ctx, loop, x0, ref, plant_params, w_inp, b_inp, w_out):
+        x, u = loop.run(x0, ref, plant_params=plant_params)
+        dev = x.device
+        ctx.loop = loop
+        ctx.tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+        ctx.like = tuple((t.shape, t.device, t.dtype) for t in (x0, w_inp, b_inp, w_out))
+        ctx.save_for_backward(x, u, ref.to(torch.float64).contiguous(),
+                              *(p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in (w_inp, b_inp, w_out)))
+        return x, u
+
+    @staticmethod
+    def backward(ctx, g_x, g_u):
+        x, u, ref, w_inp, b_inp, w_out = ctx.saved_tensors
+        g = loop_vjp(ctx.loop, x, u, ref, g_x, g_u, (w_inp, b_inp, w_out), ctx.tab)
+        like = lambda t, to: t.reshape(to[0]).to(device=to[1], dtype=to[2])
+        x0_, wi_, bi_, wo_ = ctx.like
+        return (None, like(g["g_x0"], x0_), None, None, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_),
+                like(g["g_w_out"], wo_))
+
+
+def loop_vjp(loop: "ClosedLoop", x: torch.Tensor, u: torch.Tensor, ref: torch.Tensor, g_x: torch.Tensor, g_u: torch.Tensor,
+             weights=None, plant_params=None) -> dict:
+    """The vector-Jacobian product of a noise-free :meth:`ClosedLoop.run` without recovery (``fcr_closed_loop_vjp``): from
+    the stored ``x (B,T+1,5)``, ``u (B,T)``, the ``ref`` of that run and the incoming ``g_x``, ``g_u``, a dict of fp64
+    tensors ``g_x0 (B,5)``, ``dv (B,T)`` (the gradient at the controller's clamped fp32 output), ``g_w_inp (H,3)``,
+    ``g_b_inp (H)``, ``g_w_out (H)``. ``weights``: the controller's three parameters as the run read them (default:
+    ``loop.controller``'s now); ``plant_params``: the run's. This is what ``run(differentiable=True)`` calls in its
+    backward; conventions: there."""
+    dev = x.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"ClosedLoop runs on a ROCm device only (x on {x.device})")
+    B, T = u.shape
+    if tuple(x.shape) != (B, T + 1, 5) or tuple(ref.shape) != (B, T) or tuple(g_x.shape) != (B, T + 1, 5) or \
+            tuple(g_u.shape) != (B, T):
+        raise ValueError(f"loop_vjp: x, g_x must be (B,T+1,5) and u, ref, g_u (B,T); got {tuple(x.shape)}, {tuple(g_x.shape)}, "
+                         f"{tuple(u.shape)}, {tuple(ref.shape)}, {tuple(g_u.shape)}")
+    f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
+    x, u, ref, gx, gu = f64(x), f64(u), f64(ref), f64(g_x), f64(g_u)
+    w_inp, b_inp, w_out = (t.detach().to(device=dev, dtype=torch.float32).contiguous()
+                           for t in (_controller_params(loop.controller) if weights is None else weights))
+    tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+    if tab is not None and tuple(tab.shape) not in ((28,), (B, 28)):
+        raise ValueError(f"plant_params must be a PressParams, (28,) or (B,28) with B = {B}, got shape {tuple(tab.shape)}")
+    H = w_inp.shape[0]
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+    out = {"g_x0": new(B, 5), "dv": new(B, T), "g_w_inp": new(H, 3), "g_b_inp": new(H), "g_w_out": new(H)}
+    lib = _native.load()
+    size = ctypes.c_size_t(0)
+    _native.check(lib.fcr_closed_loop_vjp_workspace_size(B, T, H, ctypes.byref(size)), "fcr_closed_loop_vjp_workspace_size")
+    ws = torch.empty(max(size.value, 8), dtype=torch.uint8, device=dev)
+    p = lambda t: t.data_ptr()
+    args = _native.FcrClosedLoopGrad(
+        B, T, loop.ts, loop.substeps, int(loop.smooth), p(ref), p(w_inp), p(b_inp), p(w_out), H,
+        (ctypes.c_double * 2)(*loop.in_scale), loop.ref_scale, loop.out_scale, p(x), p(u), p(gx), p(gu),
+        None if tab is None else p(tab), 28 if tab is not None and tab.dim() == 2 else 0,
+        p(out["g_x0"]), p(out["dv"]), p(out["g_w_inp"]), p(out["g_b_inp"]), p(out["g_w_out"]))
+    _native.check(lib.fcr_closed_loop_vjp(ctypes.byref(args), ctypes.c_void_p(p(ws)), ws.numel(),
+                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "fcr_closed_loop_vjp")
+    return out
 
 
 def _press_shape(params) -> tuple:

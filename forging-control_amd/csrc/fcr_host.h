@@ -5,6 +5,7 @@
 //                    (fcr_sur.h) and the kernels every engine shares (fcr_shared_kernels.h)
 //   fcr_wide.hip     the H > 52 rollout, the H > 52 surrogate step and the fcr_wide_bwd_cell test hook
 //   fcr_rows.hip     plant, closed loop, window gather, the supervised baseline's epoch
+//   fcr_grad.hip     the press's adjoint: vector-Jacobian products of the plant rollout and the closed loop
 // What one file needs of another goes through the functions below.
 // (The H <= 52 surrogate's kernels stay with the rollout's: compiled in a file of their own, sur_fwd_kernel<13> and
 // sur_bwd_kernel come out with another instruction schedule and register allocation — they inline the same cell

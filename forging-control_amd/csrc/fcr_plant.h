@@ -111,7 +111,7 @@ __host__ __device__ inline Coeffs derive(const double *row) {
 template <class P>
 constexpr bool kLiteral = false;   // P's members are literals: the expressions are left to the compiler as they always were
 template <>
-constexpr bool kLiteral<Nominal> = true;
+inline constexpr bool kLiteral<Nominal> = true;   // inline: the header is included by more than one translation unit
 
 // M1 T + M2 log e + M3 log e_dot + M4 / e with its roundings spelled out — fma(M2, log e, M1 T), then the ROUNDED product
 // M3 log e_dot added, then the quotient — which is what the compiler makes of the plain expression when the

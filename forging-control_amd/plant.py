@@ -132,13 +132,30 @@ def forging_rk4(x0: torch.Tensor, u: torch.Tensor, ts: float = TS_REFERENCE,
     forging_model's. ``params``: the press — a :class:`PressParams` or a ``(28,)`` row for all trajectories, or a
     ``(B, 28)`` table, one row per trajectory (``fcr_plant_rk4_press``; a shared row is read through a zero stride, not
     expanded); ``None`` is the reference's press, the call as it always was. Runs on a ROCm device only; there is no CPU
-    path."""
+    path.
+
+    Differentiable: when ``x0`` or ``u`` requires grad (and grad mode is on) the result is attached to the graph; its
+    values are the plain call's, bit for bit, and the backward is the hand-written adjoint of the RK4 step
+    (``fcr_plant_rk4_vjp``, csrc/fcr_press_grad.h), which recomputes the sub-steps from the stored
+    states. Conventions where the derivative is singular: the deformation force is differentiated only where ``y > 0``
+    and ``y_dot > 0`` (at ``y_dot == 0`` its slope is infinite and is taken as 0, so a press at rest has finite
+    gradients); the valve flow ``q = c z sign(a) sqrt(k|a|)`` has ``dq/da = dq/dz = 0`` at ``a == 0``, its branch chosen by
+    ``z >= 0`` as in the forward; the friction's slope is ``FT/0.5`` where ``|y_dot| <= 0.5`` and 0 elsewhere; the smooth
+    pressure floor's is ``0.5 (1 + p / sqrt(p^2 + eps))``. No gradient reaches ``params``. Gradients through this plant
+    grow with S: back-propagation through hundreds of steps is the caller's risk."""
+    if u.dim() == 1:
+        u = u.unsqueeze(1)
+    if torch.is_grad_enabled() and (x0.requires_grad or u.requires_grad):
+        return _ForgingRK4Grad.apply(x0, u, float(ts), int(substeps), bool(smooth), params)
+    return _forging_rk4(x0, u, ts, substeps, smooth, params)[0]
+
+
+def _forging_rk4(x0, u, ts, substeps, smooth, params):
+    """The launch of :func:`forging_rk4`: ``(x, u as the kernel read it, the parameter table or None)``."""
     if x0.device.type != "cuda" or u.device != x0.device:
         raise RuntimeError(f"forging_rk4 runs on a ROCm device only (got x0 on {x0.device}, u on {u.device})")
     if x0.dim() != 2 or x0.shape[1] != 5:
         raise ValueError(f"x0 must be (B, 5), got {tuple(x0.shape)}")
-    if u.dim() == 1:
-        u = u.unsqueeze(1)
     if u.dim() != 2 or u.shape[0] != x0.shape[0]:
         raise ValueError(f"u must be (B, S) with B = {x0.shape[0]}, got {tuple(u.shape)}")
     B, S = x0.shape[0], u.shape[1]
@@ -156,13 +173,42 @@ def forging_rk4(x0: torch.Tensor, u: torch.Tensor, ts: float = TS_REFERENCE,
                                               28 if tab.dim() == 2 else 0,
                                               ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)),
                       "fcr_plant_rk4_press")
-        return out
+        return out, uc, tab
     _native.check(lib.fcr_plant_rk4(B, S, float(ts), int(substeps), int(bool(smooth)),
                                     ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
                                     ctypes.c_void_p(out.data_ptr()),
                                     ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)),
                   "fcr_plant_rk4")
-    return out
+    return out, uc, None
+
+
+class _ForgingRK4Grad(torch.autograd.Function):
+    """:func:`forging_rk4` attached to the graph: the forward is the plain launch, the backward ``fcr_plant_rk4_vjp`` on
+    the stored states and commands."""
+
+    @staticmethod
+    def forward(ctx, x0, u, ts, substeps, smooth, params):
+        x, uc, tab = _forging_rk4(x0, u, ts, substeps, smooth, params)
+        ctx.save_for_backward(x, uc)
+        ctx.tab, ctx.step, ctx.dtypes = tab, (ts, substeps, smooth), (x0.dtype, u.dtype)
+        return x
+
+    @staticmethod
+    def backward(ctx, g_x):
+        x, uc = ctx.saved_tensors
+        B, S = uc.shape
+        ts, substeps, smooth = ctx.step
+        g = g_x.to(torch.float64).contiguous()
+        g_x0 = torch.empty(B, 5, dtype=torch.float64, device=x.device)
+        g_u = torch.empty(B, S, dtype=torch.float64, device=x.device)
+        tab = ctx.tab
+        _native.check(_native.load().fcr_plant_rk4_vjp(
+            B, S, ts, substeps, int(smooth), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
+            ctypes.c_void_p(g.data_ptr()), None if tab is None else ctypes.c_void_p(tab.data_ptr()),
+            28 if tab is not None and tab.dim() == 2 else 0, ctypes.c_void_p(g_x0.data_ptr()),
+            ctypes.c_void_p(g_u.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+            "fcr_plant_rk4_vjp")
+        return g_x0.to(ctx.dtypes[0]), g_u.to(ctx.dtypes[1]), None, None, None, None
 
 
 class ForgingRK4:

@@ -435,6 +435,53 @@ int fcr_closed_loop_run_bank_press(const fcr_closed_loop_bank *args, const doubl
                                    int64_t stride_traj, const fcr_press *model, void *stream);
 
 /*
+ * The differentiable press (a pure addition to ABI 8): the vector-Jacobian products of fcr_plant_rk4 and of the
+ * noise-free fcr_closed_loop_run without recovery, by the hand-written adjoint of the RK4 step. The
+ * caller keeps what the forward call stored and passes the gradient of its scalar with respect to every stored value.
+ *
+ *   fcr_plant_rk4_vjp: x (B,S+1,5) and u (B,S) of fcr_plant_rk4 / fcr_plant_rk4_press, g_x (B,S+1,5) = dL/dx ->
+ *     g_x0 (B,5) = dL/dx0 and g_u (B,S) = dL/du. press / stride_traj: the table the forward integrated (NULL, 0: the
+ *     reference's press). S = 0: g_x0 = g_x[:,0]. B = 0 is a no-op.
+ *   fcr_closed_loop_vjp: the forward's fields, the stored x (B,T+1,5) and u (B,T), g_x and g_u (B,T) ->
+ *     g_x0 (B,5); dv (B,T) = dL/d(the controller's clamped fp32 output); and the controller's parameter gradients in
+ *     fp64, g_w_inp (ctrl_hidden,3), g_b_inp (ctrl_hidden), g_w_out (ctrl_hidden), summed over all (b,t) in a fixed
+ *     order (no atomics: the same call twice gives the same bits). ctrl_hidden is 1..256 as in the forward. ws: device
+ *     scratch of fcr_closed_loop_vjp_workspace_size bytes. T = 0: g_x0 = g_x[:,0] and zero parameter gradients; B = 0:
+ *     zero parameter gradients (where their pointers are given).
+ *
+ * Conventions where the derivative is singular: the deformation force is differentiated only where y > 0 && y_dot > 0
+ * (at y_dot = 0 its slope is infinite and is taken as 0); the valve flow's derivatives with respect to its pressure
+ * difference a and to z are 0 at a = 0, its branch chosen by z >= 0 as in the forward; the friction's slope is FT/0.5
+ * where |y_dot| <= 0.5 and 0 elsewhere; the smooth pressure floor's is 0.5 (1 + p / sqrt(p^2 + eps)). The controller's
+ * fp32 chain is recomputed from the stored record in the forward's operation order, so its ReLU masks (ReLU'(0) = 0) and
+ * Hardtanh mask (1 only for -1 < v < 1) are the forward's; float casts are differentiated as the identity.
+ * Not covered: process / measurement noise, feasibility recovery, gradients with respect to the press parameters.
+ */
+int fcr_plant_rk4_vjp(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x, const double *u,
+                      const double *g_x, const double *press, int64_t stride_traj, double *g_x0, double *g_u,
+                      void *stream);
+
+typedef struct fcr_closed_loop_grad {
+    int32_t B, T;
+    double ts;
+    int32_t substeps, smooth;
+    const double *ref;                                   /* (B,T) */
+    const float *ctrl_w_inp, *ctrl_b_inp, *ctrl_w_out;
+    int32_t ctrl_hidden;
+    double in_scale[2];
+    double ref_scale, out_scale;
+    const double *x, *u;                                 /* the forward's outputs */
+    const double *g_x, *g_u;                             /* (B,T+1,5), (B,T): incoming */
+    const double *press;                                 /* the forward's table, or NULL: the reference's press */
+    int64_t stride_traj;                                 /* elements between trajectories' rows; 0 = shared */
+    double *g_x0, *dv;                                   /* (B,5), (B,T) */
+    double *g_w_inp, *g_b_inp, *g_w_out;                 /* (ctrl_hidden,3), (ctrl_hidden), (ctrl_hidden) fp64 */
+} fcr_closed_loop_grad;
+
+int fcr_closed_loop_vjp_workspace_size(int32_t B, int32_t T, int32_t ctrl_hidden, size_t *bytes);
+int fcr_closed_loop_vjp(const fcr_closed_loop_grad *args, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Training-sample windows: the tables of the concatenated per-trajectory
  * SequenceDatasets (Functions.py:92-132, built by Data.get_individual_dataset :479-516 and
  * ConcatDataset, UL/Main.py:270-279), resident in device memory.
