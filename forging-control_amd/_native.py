@@ -10,6 +10,8 @@ import os
 import sys
 import threading
 
+import torch
+
 _LIB_NAME = "libfcr.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _IN_TREE = os.path.join(_HERE, "lib", _LIB_NAME)
@@ -188,6 +190,67 @@ class FcrSupervised(ctypes.Structure):
     ]
 
 
+_vp, _i32, _i64, _sz, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
+_P = ctypes.POINTER
+_dims, _po, _wts, _pt, _feas, _press = _P(FcrDims), _P(FcrOptions), _P(FcrWeights), _P(FcrLossTerms), _P(FcrFeasibility), _P(FcrPress)
+# (symbol, restype, argtypes) of every call load() declares
+_SIGNATURES = (
+    ("fcr_workspace_size", _i32, [_dims, _po, _i32, _P(_sz)]),
+    ("fcr_wide_kept_windows", _i32, [_dims, _sz, _P(ctypes.c_int32)]),
+    ("fcr_forward", _i32, [_dims, _po, _wts] + [_vp] * 10 + [_i32, _vp, _sz, _vp]),
+    ("fcr_backward", _i32, [_dims, _po] + [_vp] * 9 + [_sz, _vp]),
+    ("fcr_plant_rk4", _i32, [_i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("fcr_lstm_workspace_size", _i32, [_dims, _i32, _P(_sz)]),
+    ("fcr_lstm_forward", _i32, [_dims, _wts, _vp, _vp, _i32, _vp, _sz, _vp]),
+    ("fcr_lstm_backward", _i32, [_dims, _wts, _vp, _P(_vp), _P(_vp), _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("fcr_lstm_rollout_workspace_size", _i32, [_dims, _P(_sz)]),
+    ("fcr_lstm_rollout", _i32, [_dims, _wts, _vp, _vp, _P(ctypes.c_float), _vp, _vp, _vp, _sz, _vp]),
+    ("fcr_closed_loop_run", _i32, [_P(FcrClosedLoop), _vp]),
+    ("fcr_closed_loop_run_bank", _i32, [_P(FcrClosedLoopBank), _vp]),            # a pure addition to ABI 8
+    ("fcr_feasibility_project", _i32, [_feas, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fcr_supervised_epoch", _i32, [_P(FcrSupervised), _vp]),
+    ("fcr_window_gather", _i32, [_P(FcrWindows), _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("fcr_fnn_workspace_size", _i32, [_i32, _i32, _P(_sz)]),
+    ("fcr_fnn_forward", _i32, [_i32, _i32, _i32] + [_vp] * 6),
+    ("fcr_fnn_backward", _i32, [_i32, _i32, _i32] + [_vp] * 10 + [_sz, _vp]),
+    # M controllers side by side (a pure addition to ABI 8)
+    ("fcr_many_workspace_size", _i32, [_dims, _po, _i32, _i32, _P(_sz)]),
+    ("fcr_forward_many", _i32, [_dims, _po, _i32, _wts] + [_vp] * 10 + [_i32, _vp, _sz, _vp]),
+    ("fcr_backward_many", _i32, [_dims, _po, _i32] + [_vp] * 9 + [_sz, _vp]),
+    ("fcr_fnn_forward_many", _i32, [_i32, _i32, _i32, _i32] + [_vp] * 6),
+    ("fcr_fnn_backward_many", _i32, [_i32, _i32, _i32, _i32] + [_vp] * 10 + [_sz, _vp]),
+    ("fcr_set_small_batch_limit", _i32, [_i32]), ("fcr_get_small_batch_limit", _i32, []),
+    ("fcr_set_small_pipe_limit", _i32, [_i32]), ("fcr_get_small_pipe_limit", _i32, []),
+    ("fcr_set_small_pipe_sets", _i32, [_i32]), ("fcr_get_small_pipe_sets", _i32, []),
+    ("fcr_set_wide_keep_budget", _i64, [_i64]), ("fcr_get_wide_keep_budget", _i64, []),
+    ("fcr_last_error", ctypes.c_char_p, []), ("fcr_abi_version", _i32, []),
+    ("fcr_wide_bwd_cell_workspace", _i32, [_i32, _i32, _i32, _P(_sz)]),
+    ("fcr_wide_bwd_cell", _i32, [_i32, _i32, _i32] + [_vp] * 11 + [_sz, _vp]),
+)
+# Pure additions to ABI 8 that an FCR_LIB development build may predate, each under the symbol load() probes for: the press
+# as data, the loss's terms as data, the differentiable press
+_ADDITIONS = {
+    "fcr_press_nominal": (
+        ("fcr_press_nominal", None, [_press]),
+        ("fcr_plant_rk4_press", _i32, [_i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+        ("fcr_feasibility_project_press", _i32, [_feas, _press, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+        ("fcr_closed_loop_run_bank_press", _i32, [_P(FcrClosedLoopBank), _vp, _i64, _i64, _press, _vp]),
+    ),
+    "fcr_forward_terms": (
+        ("fcr_loss_terms_default", None, [_pt, ctypes.c_float]),
+        ("fcr_forward_terms", _i32, [_dims, _po, _wts, _pt] + [_vp] * 10 + [_i32, _vp, _sz, _vp]),
+        ("fcr_backward_terms", _i32, [_dims, _po, _pt] + [_vp] * 9 + [_sz, _vp]),
+        ("fcr_forward_many_terms", _i32, [_dims, _po, _i32, _wts, _pt] + [_vp] * 10 + [_i32, _vp, _sz, _vp]),
+        ("fcr_backward_many_terms", _i32, [_dims, _po, _i32, _pt] + [_vp] * 9 + [_sz, _vp]),
+    ),
+    "fcr_plant_rk4_vjp": (
+        ("fcr_plant_rk4_vjp", _i32, [_i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+        ("fcr_closed_loop_vjp_workspace_size", _i32, [_i32, _i32, _i32, _P(_sz)]),
+        ("fcr_closed_loop_vjp", _i32, [_P(FcrClosedLoopGrad), _vp, _sz, _vp]),
+    ),
+}
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -212,122 +275,13 @@ def load() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no fallback path.")
         lib = ctypes.CDLL(LIB_PATH)
-        vp, i32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        po = ctypes.POINTER(FcrOptions)
-        lib.fcr_workspace_size.argtypes = [ctypes.POINTER(FcrDims), po, i32, ctypes.POINTER(sz)]
-        lib.fcr_workspace_size.restype = i32
-        lib.fcr_wide_kept_windows.argtypes = [ctypes.POINTER(FcrDims), sz, ctypes.POINTER(ctypes.c_int32)]
-        lib.fcr_wide_kept_windows.restype = i32
-        lib.fcr_forward.argtypes = [ctypes.POINTER(FcrDims), po, ctypes.POINTER(FcrWeights),
-                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
-        lib.fcr_forward.restype = i32
-        lib.fcr_backward.argtypes = [ctypes.POINTER(FcrDims), po, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.fcr_backward.restype = i32
-        lib.fcr_plant_rk4.argtypes = [i32, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp]
-        lib.fcr_plant_rk4.restype = i32
-        lib.fcr_lstm_workspace_size.argtypes = [ctypes.POINTER(FcrDims), i32, ctypes.POINTER(sz)]
-        lib.fcr_lstm_workspace_size.restype = i32
-        lib.fcr_lstm_forward.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(FcrWeights), vp, vp, i32, vp, sz, vp]
-        lib.fcr_lstm_forward.restype = i32
-        lib.fcr_lstm_backward.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(FcrWeights), vp,
-                                          ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp, sz, vp]
-        lib.fcr_lstm_backward.restype = i32
-        lib.fcr_lstm_rollout_workspace_size.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(sz)]
-        lib.fcr_lstm_rollout_workspace_size.restype = i32
-        lib.fcr_lstm_rollout.argtypes = [ctypes.POINTER(FcrDims), ctypes.POINTER(FcrWeights), vp, vp,
-                                         ctypes.POINTER(ctypes.c_float), vp, vp, vp, sz, vp]
-        lib.fcr_lstm_rollout.restype = i32
-        lib.fcr_closed_loop_run.argtypes = [ctypes.POINTER(FcrClosedLoop), vp]
-        lib.fcr_closed_loop_run.restype = i32
-        lib.fcr_closed_loop_run_bank.argtypes = [ctypes.POINTER(FcrClosedLoopBank), vp]   # a pure addition to ABI 8
-        lib.fcr_closed_loop_run_bank.restype = i32
-        lib.fcr_feasibility_project.argtypes = [ctypes.POINTER(FcrFeasibility), i32, vp, vp, vp, vp, vp, vp]
-        lib.fcr_feasibility_project.restype = i32
-        # the press as data (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the addition
-        # (an A/B timing against an earlier commit) loads without it; the press calls then raise AttributeError.
-        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_press_nominal"):
-            lib.fcr_press_nominal.argtypes = [ctypes.POINTER(FcrPress)]
-            lib.fcr_press_nominal.restype = None
-            lib.fcr_plant_rk4_press.argtypes = [i32, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp]
-            lib.fcr_plant_rk4_press.restype = i32
-            lib.fcr_feasibility_project_press.argtypes = [ctypes.POINTER(FcrFeasibility), ctypes.POINTER(FcrPress), i32,
-                                                          vp, vp, vp, vp, vp, vp]
-            lib.fcr_feasibility_project_press.restype = i32
-            lib.fcr_closed_loop_run_bank_press.argtypes = [ctypes.POINTER(FcrClosedLoopBank), vp, ctypes.c_int64,
-                                                           ctypes.c_int64, ctypes.POINTER(FcrPress), vp]
-            lib.fcr_closed_loop_run_bank_press.restype = i32
-        lib.fcr_supervised_epoch.argtypes = [ctypes.POINTER(FcrSupervised), vp]
-        lib.fcr_supervised_epoch.restype = i32
-        lib.fcr_window_gather.argtypes = [ctypes.POINTER(FcrWindows), i32, vp, vp, vp, vp, vp, vp]
-        lib.fcr_window_gather.restype = i32
-        lib.fcr_fnn_workspace_size.argtypes = [i32, i32, ctypes.POINTER(sz)]
-        lib.fcr_fnn_workspace_size.restype = i32
-        lib.fcr_fnn_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        lib.fcr_fnn_forward.restype = i32
-        lib.fcr_fnn_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.fcr_fnn_backward.restype = i32
-        # M controllers side by side (a pure addition to ABI 8)
-        lib.fcr_many_workspace_size.argtypes = [ctypes.POINTER(FcrDims), po, i32, i32, ctypes.POINTER(sz)]
-        lib.fcr_many_workspace_size.restype = i32
-        lib.fcr_forward_many.argtypes = [ctypes.POINTER(FcrDims), po, i32, ctypes.POINTER(FcrWeights),
-                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
-        lib.fcr_forward_many.restype = i32
-        lib.fcr_backward_many.argtypes = [ctypes.POINTER(FcrDims), po, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.fcr_backward_many.restype = i32
-        # the loss's terms as data (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the
-        # addition loads without it; calls with terms or a reference preview then raise AttributeError.
-        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_forward_terms"):
-            pt = ctypes.POINTER(FcrLossTerms)
-            lib.fcr_loss_terms_default.argtypes = [pt, ctypes.c_float]
-            lib.fcr_loss_terms_default.restype = None
-            lib.fcr_forward_terms.argtypes = [ctypes.POINTER(FcrDims), po, ctypes.POINTER(FcrWeights), pt,
-                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
-            lib.fcr_forward_terms.restype = i32
-            lib.fcr_backward_terms.argtypes = [ctypes.POINTER(FcrDims), po, pt, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-            lib.fcr_backward_terms.restype = i32
-            lib.fcr_forward_many_terms.argtypes = [ctypes.POINTER(FcrDims), po, i32, ctypes.POINTER(FcrWeights), pt,
-                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]
-            lib.fcr_forward_many_terms.restype = i32
-            lib.fcr_backward_many_terms.argtypes = [ctypes.POINTER(FcrDims), po, i32, pt, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                    vp, sz, vp]
-            lib.fcr_backward_many_terms.restype = i32
-        # the differentiable press (a pure addition to ABI 8). An FCR_LIB development build of ABI 8 from before the
-        # addition loads without it; a backward through the press then raises AttributeError.
-        if LIB_PATH == _IN_TREE or hasattr(lib, "fcr_plant_rk4_vjp"):
-            lib.fcr_plant_rk4_vjp.argtypes = [i32, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp]
-            lib.fcr_plant_rk4_vjp.restype = i32
-            lib.fcr_closed_loop_vjp_workspace_size.argtypes = [i32, i32, i32, ctypes.POINTER(sz)]
-            lib.fcr_closed_loop_vjp_workspace_size.restype = i32
-            lib.fcr_closed_loop_vjp.argtypes = [ctypes.POINTER(FcrClosedLoopGrad), vp, sz, vp]
-            lib.fcr_closed_loop_vjp.restype = i32
-        lib.fcr_fnn_forward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        lib.fcr_fnn_forward_many.restype = i32
-        lib.fcr_fnn_backward_many.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        lib.fcr_fnn_backward_many.restype = i32
-        lib.fcr_set_small_batch_limit.argtypes = [i32]
-        lib.fcr_set_small_batch_limit.restype = i32
-        lib.fcr_get_small_batch_limit.argtypes = []
-        lib.fcr_get_small_batch_limit.restype = i32
-        lib.fcr_set_small_pipe_limit.argtypes = [i32]
-        lib.fcr_set_small_pipe_limit.restype = i32
-        lib.fcr_get_small_pipe_limit.argtypes = []
-        lib.fcr_get_small_pipe_limit.restype = i32
-        lib.fcr_set_small_pipe_sets.argtypes = [i32]
-        lib.fcr_set_small_pipe_sets.restype = i32
-        lib.fcr_get_small_pipe_sets.argtypes = []
-        lib.fcr_get_small_pipe_sets.restype = i32
-        lib.fcr_set_wide_keep_budget.argtypes = [ctypes.c_int64]
-        lib.fcr_set_wide_keep_budget.restype = ctypes.c_int64
-        lib.fcr_get_wide_keep_budget.argtypes = []
-        lib.fcr_get_wide_keep_budget.restype = ctypes.c_int64
-        lib.fcr_last_error.argtypes = []
-        lib.fcr_last_error.restype = ctypes.c_char_p
-        lib.fcr_abi_version.argtypes = []
-        lib.fcr_abi_version.restype = i32
-        lib.fcr_wide_bwd_cell_workspace.argtypes = [i32, i32, i32, ctypes.POINTER(sz)]
-        lib.fcr_wide_bwd_cell_workspace.restype = i32
-        lib.fcr_wide_bwd_cell.argtypes = [i32, i32, i32] + [vp] * 11 + [sz, vp]
-        lib.fcr_wide_bwd_cell.restype = i32
+        for probe, rows in [(None, _SIGNATURES)] + list(_ADDITIONS.items()):
+            # An FCR_LIB development build of ABI 8 from before an addition (an A/B timing against an earlier commit)
+            # loads without it; the calls it lacks then raise AttributeError.
+            if probe is None or LIB_PATH == _IN_TREE or hasattr(lib, probe):
+                for name, restype, argtypes in rows:
+                    fn = getattr(lib, name)
+                    fn.restype, fn.argtypes = restype, argtypes
         if lib.fcr_abi_version() != ABI_VERSION:
             raise NativeError(f"libfcr ABI {lib.fcr_abi_version()} != expected {ABI_VERSION}")
         _lib = lib
@@ -338,6 +292,11 @@ def check(rc: int, what: str) -> None:
     if rc != FCR_OK:
         msg = load().fcr_last_error().decode(errors="replace")
         raise NativeError(f"{what} failed ({ERRORS.get(rc, rc)}): {msg}")
+
+
+def stream(device) -> ctypes.c_void_p:
+    """The current HIP stream of ``device``, as the ``void *stream`` every launching call takes."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def set_small_batch_limit(max_batch: int) -> int:

@@ -119,21 +119,87 @@ class FeasibilityRecovery:
         flag = torch.empty(B, dtype=torch.int32, device=dev)
         v = torch.empty(B, dtype=torch.float64, device=dev) if return_violation else None
         f = self.struct()
+        name, extra = "fcr_feasibility_project", ()
         if self.model_params is not None:
-            model = self.model_params.struct()
-            _native.check(_native.load().fcr_feasibility_project_press(
-                ctypes.byref(f), ctypes.byref(model), B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
-                None if v is None else v.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                "fcr_feasibility_project_press")
-            return (u, flag, v) if return_violation else (u, flag)
-        _native.check(_native.load().fcr_feasibility_project(
-            ctypes.byref(f), B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
-            None if v is None else v.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-            "fcr_feasibility_project")
+            model = self.model_params.struct()               # stays alive over the call below
+            name, extra = "fcr_feasibility_project_press", (ctypes.byref(model),)
+        _native.check(getattr(_native.load(), name)(
+            ctypes.byref(f), *extra, B, xc.data_ptr(), uc.data_ptr(), u.data_ptr(), flag.data_ptr(),
+            None if v is None else v.data_ptr(), _native.stream(dev)), name)
         return (u, flag, v) if return_violation else (u, flag)
 
 
-class ClosedLoop:
+def _per_model(name, t, M, tail):
+    """Whether ``t`` is ``(M,) + tail`` (True) or ``tail``, one copy shared by all models (False); ``M = None``: the
+    single loop, ``tail`` alone."""
+    if tuple(t.shape) == tail:
+        return False
+    if M is not None and tuple(t.shape) == (M,) + tail:
+        return True
+    forms = f"(B,T,{tail[-1]}) = {tail}" if M is None else f"{tail} (shared by all models) or {(M,) + tail}"
+    raise ValueError(f"{name} must be {forms}, got {tuple(t.shape)}")
+
+
+class _LoopConfig:
+    """What :class:`ClosedLoop` and :class:`ClosedLoopBank` hold alike — the controller's scales as the kernels take
+    them, ``ts``, ``substeps``, ``smooth`` — and how both turn a run's inputs into the arguments of its launch."""
+
+    def __init__(self, scalers, ts, substeps, smooth):
+        if isinstance(scalers, _LoopConfig):                 # another loop's scales, as they are
+            self.in_scale, self.ref_scale, self.out_scale = scalers.in_scale, scalers.ref_scale, scalers.out_scale
+        else:
+            s_in = _scale(scalers["input"])
+            self.in_scale = (float(s_in[0]), float(s_in[1]))
+            self.ref_scale = float(_scale(scalers["y_dot"])[0])
+            self.out_scale = float(_scale(scalers["output"])[0])
+        self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
+
+    def _prepare(self, M, weights, x0, ref, process_noise, meas_noise, feasibility, store=True):
+        """The checks and conversions of a run: ``M = None`` for one model (inputs without a leading M), else the bank's M.
+        Returns ``(dev, B, T, stacked, out, prefix, keep)``: which inputs carry a leading M, the per-step outputs
+        (``x, u, u_nn, flag``; ``None`` where not stored), the constructor arguments of ``FcrClosedLoop`` (the fields
+        ``FcrClosedLoopBank`` begins with), and what must stay alive over the call."""
+        who, dev = type(self).__name__, x0.device
+        noises = {"process_noise": process_noise, "meas_noise": meas_noise}
+
+        def on_device():
+            if dev.type != "cuda" or ref.device != dev:
+                raise RuntimeError(f"{who} runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
+
+        if M is None:
+            on_device()                                      # one model: the device first; the bank: the shapes first
+        dims = (2,) if M is None else (2, 3)
+        if x0.dim() not in dims or x0.shape[-1] != 5 or ref.dim() not in dims or (M is None and ref.shape[0] != x0.shape[0]):
+            forms = "(B,5) and ref (B,T)" if M is None else "(B,5) or (M,B,5) and ref (B,T) or (M,B,T)"
+            raise ValueError(f"x0 must be {forms}; got {tuple(x0.shape)}, {tuple(ref.shape)}")
+        B, T = x0.shape[-2], ref.shape[-1]
+        stacked = {"x0": _per_model("x0", x0, M, (B, 5)), "ref": _per_model("ref", ref, M, (B, T))}
+        for name, n in noises.items():
+            stacked[name] = n is not None and _per_model(name, n, M, (B, T, 5))
+        if M is not None:
+            on_device()
+        for name, n in noises.items():
+            if n is not None and n.device != dev:
+                raise RuntimeError(f"{name} must be on {dev}, found it on {n.device}")
+        f64 = lambda t: None if t is None else t.to(torch.float64).contiguous()
+        x0c, refc, wc, vc = f64(x0), f64(ref), f64(process_noise), f64(meas_noise)
+        W_inp, b_inp, W_out = (p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in weights)
+        lead = () if M is None else (M,)
+        new = lambda *shape, dtype=torch.float64: torch.empty(*lead, *shape, dtype=dtype, device=dev) if store else None
+        out = {"x": new(B, T + 1, 5), "u": new(B, T), "u_nn": None, "flag": None}
+        f_struct = None
+        if feasibility is not None:
+            f_struct = feasibility.struct()
+            out["u_nn"], out["flag"] = new(B, T), new(B, T, dtype=torch.int32)
+        p = lambda t: None if t is None else t.data_ptr()
+        prefix = (B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp), p(b_inp), p(W_out),
+                  W_inp.shape[-2], (ctypes.c_double * 2)(*self.in_scale), self.ref_scale, self.out_scale, p(out["x"]),
+                  p(out["u"]), p(wc), p(vc), None if f_struct is None else ctypes.pointer(f_struct), p(out["u_nn"]),
+                  p(out["flag"]))
+        return dev, B, T, stacked, out, prefix, (x0c, refc, wc, vc, W_inp, b_inp, W_out, f_struct)
+
+
+class ClosedLoop(_LoopConfig):
     """Controller + press for B trajectories over T steps: ``run(x0 (B,5), ref (B,T))`` ->
     ``(x (B,T+1,5), u (B,T))`` as fp64 device tensors.
 
@@ -142,13 +208,9 @@ class ClosedLoop:
 
     def __init__(self, controller, scalers: dict, ts: float = TS_REFERENCE, substeps: int = SUBSTEPS_REFERENCE,
                  smooth: bool = True, plant_params=None):
+        super().__init__(scalers, ts, substeps, smooth)
         self.controller = controller
         self.plant_params = plant_params                     # the default of run(plant_params=...)
-        s_in = _scale(scalers["input"])
-        self.in_scale = (float(s_in[0]), float(s_in[1]))
-        self.ref_scale = float(_scale(scalers["y_dot"])[0])
-        self.out_scale = float(_scale(scalers["output"])[0])
-        self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
             meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, plant_params=None,
@@ -203,43 +265,13 @@ class ClosedLoop:
             if feasibility is None:
                 return r["x"][0], r["u"][0]
             return r["x"][0], r["u"][0], {"u_nn": r["u_nn"][0], "flag": r["flag"][0]}
-        dev = x0.device
-        if dev.type != "cuda" or ref.device != dev:
-            raise RuntimeError(f"ClosedLoop runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
-        if x0.dim() != 2 or x0.shape[1] != 5 or ref.dim() != 2 or ref.shape[0] != x0.shape[0]:
-            raise ValueError(f"x0 must be (B,5) and ref (B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
-        B, T = x0.shape[0], ref.shape[1]
-        noise = []
-        for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
-            if n is None:
-                noise.append(None)
-                continue
-            if tuple(n.shape) != (B, T, 5):
-                raise ValueError(f"{name} must be (B,T,5) = {(B, T, 5)}, got {tuple(n.shape)}")
-            if n.device != dev:
-                raise RuntimeError(f"{name} must be on {dev}, found it on {n.device}")
-            noise.append(n.to(torch.float64).contiguous())
-        W_inp, b_inp, W_out = (p.detach().to(device=dev, dtype=torch.float32).contiguous()
-                               for p in _controller_params(self.controller))
-        x0c = x0.to(torch.float64).contiguous()
-        refc = ref.to(torch.float64).contiguous()
-        x = torch.empty(B, T + 1, 5, dtype=torch.float64, device=dev)
-        u = torch.empty(B, T, dtype=torch.float64, device=dev)
-        p = lambda t: t.data_ptr()
-        feas, info = (), None
-        if feasibility is not None:
-            info = {"u_nn": torch.empty(B, T, dtype=torch.float64, device=dev),
-                    "flag": torch.empty(B, T, dtype=torch.int32, device=dev)}
-            f_struct = feasibility.struct()                  # stays alive over the call below
-            feas = (ctypes.pointer(f_struct), p(info["u_nn"]), p(info["flag"]))
-        args = _native.FcrClosedLoop(B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp),
-                                     p(b_inp), p(W_out), W_inp.shape[0], (ctypes.c_double * 2)(*self.in_scale),
-                                     self.ref_scale, self.out_scale, p(x), p(u),
-                                     *(None if n is None else p(n) for n in noise), *feas)
-        _native.check(_native.load().fcr_closed_loop_run(ctypes.byref(args),
-                                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                      "fcr_closed_loop_run")
-        return (x, u) if info is None else (x, u, info)
+        dev, _, _, _, out, prefix, keep = self._prepare(None, _controller_params(self.controller), x0, ref, process_noise,
+                                                        meas_noise, feasibility)
+        args = _native.FcrClosedLoop(*prefix)
+        _native.check(_native.load().fcr_closed_loop_run(ctypes.byref(args), _native.stream(dev)), "fcr_closed_loop_run")
+        if feasibility is None:
+            return out["x"], out["u"]
+        return out["x"], out["u"], {"u_nn": out["u_nn"], "flag": out["flag"]}
 
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
              process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
@@ -328,8 +360,7 @@ def loop_vjp(loop: "ClosedLoop", x: torch.Tensor, u: torch.Tensor, ref: torch.Te
         (ctypes.c_double * 2)(*loop.in_scale), loop.ref_scale, loop.out_scale, p(x), p(u), p(gx), p(gu),
         None if tab is None else p(tab), 28 if tab is not None and tab.dim() == 2 else 0,
         p(out["g_x0"]), p(out["dv"]), p(out["g_w_inp"]), p(out["g_b_inp"]), p(out["g_w_out"]))
-    _native.check(lib.fcr_closed_loop_vjp(ctypes.byref(args), ctypes.c_void_p(p(ws)), ws.numel(),
-                                          ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+    _native.check(lib.fcr_closed_loop_vjp(ctypes.byref(args), ctypes.c_void_p(p(ws)), ws.numel(), _native.stream(dev)),
                   "fcr_closed_loop_vjp")
     return out
 
@@ -369,7 +400,7 @@ def _shadow_track(first: torch.Tensor, u: torch.Tensor, simulator, s_in, s_out, 
 METRIC_KEYS = ("MAE", "RMSE", "R2", "max_err", "Command", "du_rms", "viol_max", "viol_frac", "flag1_frac", "flag2_frac")
 
 
-class ClosedLoopBank:
+class ClosedLoopBank(_LoopConfig):
     """:class:`ClosedLoop` for the M controllers of a :class:`~.many.ControllerBank` (one hidden width, one set of
     scalers): M x B trajectories over T steps in ONE launch (``fcr_closed_loop_run_bank``), and the numbers the
     reference tabulates per seed (``metrics`` / ``other_metrics``, Functions.py:751-822) from the same launch plus one
@@ -393,29 +424,15 @@ class ClosedLoopBank:
         for name in ("w_inp", "b_inp", "w_out"):
             if not hasattr(bank, name):
                 raise TypeError(f"ClosedLoopBank needs a ControllerBank (stacked w_inp, b_inp, w_out); got {type(bank).__name__}")
+        super().__init__(scalers, ts, substeps, smooth)
         self.bank = bank
-        s_in = _scale(scalers["input"])
-        self.in_scale = (float(s_in[0]), float(s_in[1]))
-        self.ref_scale = float(_scale(scalers["y_dot"])[0])
-        self.out_scale = float(_scale(scalers["output"])[0])
-        self.ts, self.substeps, self.smooth = float(ts), int(substeps), bool(smooth)
 
     @classmethod
     def of_loop(cls, loop: "ClosedLoop") -> "ClosedLoopBank":
-        """The bank of ONE model that runs ``loop``'s controller with its scales and step (built through ``__init__``)."""
+        """The bank of ONE model that runs ``loop``'s controller with its scales and step."""
         w_inp, b_inp, w_out = (p.detach() for p in _controller_params(loop.controller))
         bank = types.SimpleNamespace(w_inp=w_inp[None], b_inp=b_inp[None], w_out=w_out.reshape(1, -1))
-        scalers = {"input": np.array(loop.in_scale), "y_dot": loop.ref_scale, "output": loop.out_scale}
-        return cls(bank, scalers, loop.ts, loop.substeps, loop.smooth)
-
-    @staticmethod
-    def _per_model(name, t, M, tail):
-        """Whether ``t`` is ``(M,) + tail`` (True) or ``tail``, one copy shared by all models (False)."""
-        if tuple(t.shape) == tail:
-            return False
-        if tuple(t.shape) == (M,) + tail:
-            return True
-        raise ValueError(f"{name} must be {tail} (shared by all models) or {(M,) + tail}, got {tuple(t.shape)}")
+        return cls(bank, loop, loop.ts, loop.substeps, loop.smooth)
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
             meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
@@ -433,59 +450,32 @@ class ClosedLoopBank:
         is what the violation statistics then measure. ``None`` (and no ``model_params``) is the call as it always was:
         ``fcr_closed_loop_run_bank`` and its kernels; otherwise ``fcr_closed_loop_run_bank_press``."""
         M = self.bank.w_inp.shape[0]
-        if x0.dim() not in (2, 3) or x0.shape[-1] != 5 or ref.dim() not in (2, 3):
-            raise ValueError(f"x0 must be (B,5) or (M,B,5) and ref (B,T) or (M,B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
-        B, T = x0.shape[-2], ref.shape[-1]
+        dev, B, T, stacked, out, prefix, keep = self._prepare(M, (self.bank.w_inp, self.bank.b_inp, self.bank.w_out), x0, ref,
+                                                              process_noise, meas_noise, feasibility, store)
         if plant_params is not None and _press_shape(plant_params) not in ((28,), (B, 28), (M, B, 28)):
             raise ValueError(f"plant_params must be a PressParams, (28,), (B,28) = {(B, 28)} or (M,B,28) = {(M, B, 28)}, "
                              f"got shape {_press_shape(plant_params)}")
-        stacked = {"x0": self._per_model("x0", x0, M, (B, 5)), "ref": self._per_model("ref", ref, M, (B, T))}
-        for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
-            stacked[name] = n is not None and self._per_model(name, n, M, (B, T, 5))
-        dev = x0.device
-        if dev.type != "cuda" or ref.device != dev:
-            raise RuntimeError(f"ClosedLoopBank runs on a ROCm device only (x0 on {x0.device}, ref on {ref.device})")
-        for name, n in (("process_noise", process_noise), ("meas_noise", meas_noise)):
-            if n is not None and n.device != dev:
-                raise RuntimeError(f"{name} must be on {dev}, found it on {n.device}")
         if p_bounds is None:
             p_bounds = (feasibility.p1, feasibility.p2) if feasibility is not None else ((0.0, 32e6), (0.0, 32e6))
         (p1_lo, p1_hi), (p2_lo, p2_hi) = p_bounds
-        f64 = lambda t: None if t is None else t.to(torch.float64).contiguous()
-        x0c, refc, wc, vc = f64(x0), f64(ref), f64(process_noise), f64(meas_noise)
-        W_inp, b_inp, W_out = (p.detach().to(device=dev, dtype=torch.float32).contiguous()
-                               for p in (self.bank.w_inp, self.bank.b_inp, self.bank.w_out))
-        new = lambda *shape, dtype=torch.float64: torch.empty(*shape, dtype=dtype, device=dev)
-        out = {"x": new(M, B, T + 1, 5) if store else None, "u": new(M, B, T) if store else None, "u_nn": None, "flag": None}
-        f_struct = None
-        if feasibility is not None:
-            f_struct = feasibility.struct()                  # stays alive over the call below
-            if store:
-                out["u_nn"], out["flag"] = new(M, B, T), new(M, B, T, dtype=torch.int32)
-        out["x_final"], out["traj_stats"] = new(M, B, 5), new(M, B, 6)
-        out["traj_counts"] = new(M, B, 3, dtype=torch.int32)
-        summary = new(M, 10)
-        p = lambda t: None if t is None else t.data_ptr()
+        new = lambda *shape, dtype=torch.float64: torch.empty(M, B, *shape, dtype=dtype, device=dev)
+        out["x_final"], out["traj_stats"], out["traj_counts"] = new(5), new(6), new(3, dtype=torch.int32)
+        summary = torch.empty(M, 10, dtype=torch.float64, device=dev)
+        p = lambda t: t.data_ptr()
         stride = lambda name, per: per if stacked[name] else 0
+        args = _native.FcrClosedLoopBank(
+            *prefix, M, stride("x0", B * 5), stride("ref", B * T), stride("process_noise", B * T * 5),
+            stride("meas_noise", B * T * 5), float(p1_lo), float(p1_hi), float(p2_lo), float(p2_hi), p(out["traj_stats"]),
+            p(out["traj_counts"]), p(out["x_final"]), p(summary))
         model = None if feasibility is None else feasibility.model_params
-        table = None
+        name, extra = "fcr_closed_loop_run_bank", ()
         if plant_params is not None or model is not None:
             table = as_press_table(PressParams() if plant_params is None else plant_params, dev, "plant_params")
-        args = _native.FcrClosedLoopBank(
-            B, T, self.ts, self.substeps, int(self.smooth), p(x0c), p(refc), p(W_inp), p(b_inp), p(W_out), W_inp.shape[1],
-            (ctypes.c_double * 2)(*self.in_scale), self.ref_scale, self.out_scale, p(out["x"]), p(out["u"]), p(wc), p(vc),
-            None if f_struct is None else ctypes.pointer(f_struct), p(out["u_nn"]), p(out["flag"]), M,
-            stride("x0", B * 5), stride("ref", B * T), stride("process_noise", B * T * 5), stride("meas_noise", B * T * 5),
-            float(p1_lo), float(p1_hi), float(p2_lo), float(p2_hi), p(out["traj_stats"]), p(out["traj_counts"]),
-            p(out["x_final"]), p(summary))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if table is None:
-            _native.check(_native.load().fcr_closed_loop_run_bank(ctypes.byref(args), stream), "fcr_closed_loop_run_bank")
-        else:
             m_struct = None if model is None else model.struct()
-            _native.check(_native.load().fcr_closed_loop_run_bank_press(
-                ctypes.byref(args), p(table), B * 28 if table.dim() == 3 else 0, 28 if table.dim() >= 2 else 0,
-                None if m_struct is None else ctypes.byref(m_struct), stream), "fcr_closed_loop_run_bank_press")
+            name = "fcr_closed_loop_run_bank_press"
+            extra = (p(table), B * 28 if table.dim() == 3 else 0, 28 if table.dim() >= 2 else 0,
+                     None if m_struct is None else ctypes.byref(m_struct))
+        _native.check(getattr(_native.load(), name)(ctypes.byref(args), *extra, _native.stream(dev)), name)
         if M == 0 or B == 0:
             summary.zero_()
         out["metrics"] = {k: summary[:, i] for i, k in enumerate(METRIC_KEYS)}
@@ -511,7 +501,7 @@ class ClosedLoopBank:
         if feasibility is not None:
             results["u_nn"], results["feas_flag"] = r["u_nn"], r["flag"]
         if lstm_noise is not None:
-            if self._per_model("lstm_noise", lstm_noise, M, (B, T, 4)):
+            if _per_model("lstm_noise", lstm_noise, M, (B, T, 4)):
                 lstm_noise = lstm_noise.reshape(M * B, T, 4)
             else:
                 lstm_noise = lstm_noise.expand(M, B, T, 4).reshape(M * B, T, 4)

@@ -23,8 +23,7 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_stream = _native.stream
 
 
 class FNNFunction(torch.autograd.Function):

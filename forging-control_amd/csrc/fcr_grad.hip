@@ -1,43 +1,31 @@
 // fcr_grad.hip — C ABI of the press's adjoint (fcr_press_grad.h): the vector-Jacobian product of the open-loop RK4
 // rollout (fcr_plant_rk4_vjp) and of the controller + press closed loop (fcr_closed_loop_vjp). Validation before any
-// device call; stream-ordered launches; no allocation.
+// device call, by the checks the press rows share (fcr_press_host.h); stream-ordered launches; no allocation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "fcr.h"
 #include "fcr_host.h"
 #include "fcr_press_grad.h"
+#include "fcr_press_host.h"
 
 using namespace fcr;
 
 namespace {
 
-int check_step(const char *who, double ts, int substeps) {
-    if (substeps < 1 || substeps > 4096) return fail(FCR_EINVAL, "%s: substeps=%d must be 1..4096", who, substeps);
-    if (!(ts > 0.0) || ts > 1e6) return fail(FCR_EINVAL, "%s: ts=%g must be a positive time step", who, ts);
-    return FCR_OK;
-}
-
-// a parameter table's pointer and stride (NULL = the reference's press; then the stride must be 0), or a message
-int check_press(const char *who, const double *press, long long stride_traj) {
-    if (stride_traj < 0 || stride_traj % plant::kPressFields)
-        return fail(FCR_EINVAL, "%s: stride_traj=%lld must be 0 (shared) or a positive multiple of %d", who, stride_traj,
-                    plant::kPressFields);
-    if (!press && stride_traj) return fail(FCR_EINVAL, "%s: stride_traj=%lld without a parameter table", who, stride_traj);
-    if (((uintptr_t)press) & 7) return fail(FCR_EINVAL, "%s: the parameter table must be 8-byte aligned (fp64)", who);
-    return FCR_OK;
-}
-
 size_t param_workspace(int B, int T, int hidden) {
     return align_up((size_t)press_grad::param_blocks((long long)B * T) * hidden * 5 * sizeof(double));
 }
 
-// kernel[smooth][kept][table]
-#define FCR_GRAD_TABLE(kernel)                                                                                          \
-    {{{kernel<false, false, plant::Nominal>, kernel<false, false, plant::Coeffs>},                                      \
-      {kernel<false, true, plant::Nominal>, kernel<false, true, plant::Coeffs>}},                                       \
-     {{kernel<true, false, plant::Nominal>, kernel<true, false, plant::Coeffs>},                                        \
-      {kernel<true, true, plant::Nominal>, kernel<true, true, plant::Coeffs>}}}
+// the press policy of an adjoint kernel: the table's rows, or the reference's press (press = NULL)
+template <bool TABLE>
+using Press = std::conditional_t<TABLE, plant::Coeffs, plant::Nominal>;
+
+// a parameter table's stride and pointer (NULL = the reference's press; then the stride must be 0), or a message
+int check_table(const char *who, const double *press, long long stride_traj, int B) {
+    if (const int rc = check_table_strides(who, 0, stride_traj, B)) return rc;
+    return check_table_pointer(who, press, false, stride_traj);
+}
 
 }  // namespace
 
@@ -47,23 +35,21 @@ int fcr_plant_rk4_vjp(int32_t B, int32_t S, double ts, int32_t substeps, int32_t
                       const double *g_x, const double *press, int64_t stride_traj, double *g_x0, double *g_u,
                       void *stream) {
     const char *who = "fcr_plant_rk4_vjp";
-    if (B < 0 || S < 0) return fail(FCR_EINVAL, "%s: B=%d, S=%d must be >= 0", who, B, S);
-    if (const int rc = check_step(who, ts, substeps)) return rc;
-    if (smooth != 0 && smooth != 1) return fail(FCR_EINVAL, "%s: smooth=%d must be 0 or 1", who, smooth);
-    if ((long long)B * (S + 1) * 5 > (1LL << 40)) return fail(FCR_EINVAL, "%s: B*(S+1) too large", who);
-    if (const int rc = check_press(who, press, stride_traj)) return rc;
+    if (const int rc = check_batch(who, B, S, "S")) return rc;
+    if (const int rc = check_step(who, "", ts, substeps)) return rc;
+    if (const int rc = check_smooth(who, smooth)) return rc;
+    if (const int rc = check_table(who, press, stride_traj, B)) return rc;
     if (B == 0) return FCR_OK;
     if (!x || !g_x || !g_x0 || (S > 0 && (!u || !g_u))) return fail(FCR_EINVAL, "%s: a required pointer is NULL", who);
     if ((((uintptr_t)x) | ((uintptr_t)u) | ((uintptr_t)g_x) | ((uintptr_t)g_x0) | ((uintptr_t)g_u)) & 7)
         return fail(FCR_EINVAL, "%s: buffers must be 8-byte aligned (fp64)", who);
-    using press_grad::plant_rk4_vjp_kernel;
-    static constexpr decltype(&plant_rk4_vjp_kernel<false, false, plant::Nominal>) k[2][2][2] =
-        FCR_GRAD_TABLE(plant_rk4_vjp_kernel);
+    const auto k = select([](auto sm, auto kept, auto table) {
+        return &press_grad::plant_rk4_vjp_kernel<sm(), kept(), Press<table()>>; },
+        smooth, substeps == press_grad::kKeptSubsteps, press != nullptr);
     const dim3 grid((B + press_grad::kGradBlock - 1) / press_grad::kGradBlock);
     // S = 0 launches too: g_x0 = g_x[:, 0]
-    hipLaunchKernelGGL(k[smooth][substeps == press_grad::kKeptSubsteps][press != nullptr], grid,
-                       dim3(press_grad::kGradBlock), 0, (hipStream_t)stream, B, S, ts / substeps, substeps, x, u, g_x, press,
-                       (long long)stride_traj, g_x0, g_u);
+    hipLaunchKernelGGL(k, grid, dim3(press_grad::kGradBlock), 0, (hipStream_t)stream, B, S, ts / substeps, substeps, x, u, g_x,
+                       press, (long long)stride_traj, g_x0, g_u);
     return launch_check("plant_rk4_vjp_kernel");
 }
 
@@ -71,7 +57,7 @@ int fcr_closed_loop_vjp_workspace_size(int32_t B, int32_t T, int32_t ctrl_hidden
     const char *who = "fcr_closed_loop_vjp_workspace_size";
     if (!bytes) return fail(FCR_EINVAL, "%s: bytes is NULL", who);
     *bytes = 0;
-    if (B < 0 || T < 0) return fail(FCR_EINVAL, "%s: B=%d, T=%d must be >= 0", who, B, T);
+    if (const int rc = check_batch(who, B, T, "T", false)) return rc;
     if (ctrl_hidden < 1 || ctrl_hidden > press_grad::kMaxHidden)
         return fail(FCR_EUNSUPPORTED, "%s: ctrl_hidden=%d: built for 1..%d", who, ctrl_hidden, press_grad::kMaxHidden);
     *bytes = param_workspace(B, T, ctrl_hidden);
@@ -80,16 +66,8 @@ int fcr_closed_loop_vjp_workspace_size(int32_t B, int32_t T, int32_t ctrl_hidden
 
 int fcr_closed_loop_vjp(const fcr_closed_loop_grad *c, void *ws, size_t ws_bytes, void *stream) {
     const char *who = "fcr_closed_loop_vjp";
-    if (!c) return fail(FCR_EINVAL, "%s: args is NULL", who);
-    if (c->B < 0 || c->T < 0) return fail(FCR_EINVAL, "%s: B=%d, T=%d must be >= 0", who, c->B, c->T);
-    if (const int rc = check_step(who, c->ts, c->substeps)) return rc;
-    if (c->smooth != 0 && c->smooth != 1) return fail(FCR_EINVAL, "%s: smooth=%d must be 0 or 1", who, c->smooth);
-    if (c->ctrl_hidden < 1 || c->ctrl_hidden > press_grad::kMaxHidden)
-        return fail(FCR_EUNSUPPORTED, "%s: ctrl_hidden=%d: built for 1..%d", who, c->ctrl_hidden, press_grad::kMaxHidden);
-    if (!(c->in_scale[0] > 0.0) || !(c->in_scale[1] > 0.0) || !(c->ref_scale > 0.0) || !(c->out_scale > 0.0))
-        return fail(FCR_EINVAL, "%s: scaler scales must be positive", who);
-    if ((long long)c->B * (c->T + 1) * 5 > (1LL << 40)) return fail(FCR_EINVAL, "%s: B*(T+1) too large", who);
-    if (const int rc = check_press(who, c->press, c->stride_traj)) return rc;
+    if (const int rc = check_loop(who, c, press_grad::kMaxHidden, true)) return rc;
+    if (const int rc = check_table(who, c->press, c->stride_traj, c->B)) return rc;
     if (!c->g_w_inp || !c->g_b_inp || !c->g_w_out) {
         if (c->B == 0) return FCR_OK;                          // an empty batch with nothing to zero
         return fail(FCR_EINVAL, "%s: a parameter gradient is NULL", who);
@@ -114,11 +92,10 @@ int fcr_closed_loop_vjp(const fcr_closed_loop_grad *c, void *ws, size_t ws_bytes
                                c->x, c->u, c->g_x, c->g_u, c->press, (long long)c->stride_traj, c->g_x0, c->dv};
     const dim3 block(press_grad::kGradBlock);
     if (c->B > 0) {   // T = 0 launches too: g_x0 = g_x[:, 0]
-        using press_grad::closed_loop_vjp_kernel;
-        static constexpr decltype(&closed_loop_vjp_kernel<false, false, plant::Nominal>) k[2][2][2] =
-            FCR_GRAD_TABLE(closed_loop_vjp_kernel);
-        hipLaunchKernelGGL(k[c->smooth][c->substeps == press_grad::kKeptSubsteps][c->press != nullptr],
-                           dim3((c->B + press_grad::kGradBlock - 1) / press_grad::kGradBlock), block, 0, s, a);
+        const auto k = select([](auto sm, auto kept, auto table) {
+            return &press_grad::closed_loop_vjp_kernel<sm(), kept(), Press<table()>>; },
+            c->smooth, c->substeps == press_grad::kKeptSubsteps, c->press != nullptr);
+        hipLaunchKernelGGL(k, dim3((c->B + press_grad::kGradBlock - 1) / press_grad::kGradBlock), block, 0, s, a);
         if (const int rc = launch_check("closed_loop_vjp_kernel")) return rc;
     }
     const int blocks = rows ? press_grad::param_blocks((long long)c->B * c->T) : 0;

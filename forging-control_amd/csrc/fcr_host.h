@@ -4,9 +4,11 @@
 //   fcr_rollout.hip  the H <= 52 rollout (fused, small-batch, pipelined kernels), the H <= 52 surrogate step
 //                    (fcr_sur.h) and the kernels every engine shares (fcr_shared_kernels.h)
 //   fcr_wide.hip     the H > 52 rollout, the H > 52 surrogate step and the fcr_wide_bwd_cell test hook
-//   fcr_rows.hip     plant, closed loop, window gather, the supervised baseline's epoch
+//   fcr_rows.hip     plant, closed loop and bank, feasibility projection, window gather, the supervised baseline's epoch
 //   fcr_grad.hip     the press's adjoint: vector-Jacobian products of the plant rollout and the closed loop
-// What one file needs of another goes through the functions below.
+// What one file needs of another goes through the functions below. The argument checks fcr_rows.hip and fcr_grad.hip
+// share, and their choice of a kernel instantiation from run-time flags, are in the host-only fcr_press_host.h: it
+// includes fcr_plant.h, so only those two files include it.
 // (The H <= 52 surrogate's kernels stay with the rollout's: compiled in a file of their own, sur_fwd_kernel<13> and
 // sur_bwd_kernel come out with another instruction schedule and register allocation — they inline the same cell
 // functions as fcr_fwd_kernel / fcr_bwd_kernel, and the compiler's order of doing so follows what else is in the file.)

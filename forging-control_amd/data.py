@@ -87,7 +87,7 @@ class SequenceWindows:
         lib = _native.load()
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         _native.check(lib.fcr_window_gather(ctypes.byref(self._tables), B, p(idx), p(x), p(y), p(z), p(self._bad),
-                                            ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                                            _native.stream(self.device)),
                       "fcr_window_gather")
         if check and int(self._bad.item()):
             raise IndexError(f"{int(self._bad.item())} index(es) outside [0, {len(self)})")

@@ -162,24 +162,16 @@ def _forging_rk4(x0, u, ts, substeps, smooth, params):
     x0c = x0.to(torch.float64).contiguous()
     uc = u.to(torch.float64).contiguous()
     out = torch.empty(B, S + 1, 5, dtype=torch.float64, device=x0.device)
-    lib = _native.load()
+    tab, name, extra = None, "fcr_plant_rk4", ()
     if params is not None:
         tab = as_press_table(params, x0.device)
         if tuple(tab.shape) not in ((28,), (B, 28)):
             raise ValueError(f"params must be a PressParams, (28,) or (B, 28) = {(B, 28)}, got {tuple(tab.shape)}")
-        _native.check(lib.fcr_plant_rk4_press(B, S, float(ts), int(substeps), int(bool(smooth)),
-                                              ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
-                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(tab.data_ptr()),
-                                              28 if tab.dim() == 2 else 0,
-                                              ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)),
-                      "fcr_plant_rk4_press")
-        return out, uc, tab
-    _native.check(lib.fcr_plant_rk4(B, S, float(ts), int(substeps), int(bool(smooth)),
-                                    ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
-                                    ctypes.c_void_p(out.data_ptr()),
-                                    ctypes.c_void_p(torch.cuda.current_stream(x0.device).cuda_stream)),
-                  "fcr_plant_rk4")
-    return out, uc, None
+        name, extra = "fcr_plant_rk4_press", (ctypes.c_void_p(tab.data_ptr()), 28 if tab.dim() == 2 else 0)
+    _native.check(getattr(_native.load(), name)(B, S, float(ts), int(substeps), int(bool(smooth)),
+                                                ctypes.c_void_p(x0c.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
+                                                ctypes.c_void_p(out.data_ptr()), *extra, _native.stream(x0.device)), name)
+    return out, uc, tab
 
 
 class _ForgingRK4Grad(torch.autograd.Function):
@@ -206,7 +198,7 @@ class _ForgingRK4Grad(torch.autograd.Function):
             B, S, ts, substeps, int(smooth), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
             ctypes.c_void_p(g.data_ptr()), None if tab is None else ctypes.c_void_p(tab.data_ptr()),
             28 if tab is not None and tab.dim() == 2 else 0, ctypes.c_void_p(g_x0.data_ptr()),
-            ctypes.c_void_p(g_u.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)),
+            ctypes.c_void_p(g_u.data_ptr()), _native.stream(x.device)),
             "fcr_plant_rk4_vjp")
         return g_x0.to(ctx.dtypes[0]), g_u.to(ctx.dtypes[1]), None, None, None, None
 

@@ -21,8 +21,7 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_stream = _native.stream
 
 
 def make_dims(B, N, H, layers, ctrl_hidden, alpha, in_dim=5, out_dim=4, ctrl_in=3, L=WINDOW_ROWS, precision=0):

@@ -51,7 +51,7 @@ class LSTMFunction(torch.autograd.Function):
                       "fcr_lstm_workspace_size")
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         y = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _native.stream(dev)
         _native.check(lib.fcr_lstm_forward(ctypes.byref(dims), ctypes.byref(w), _p(xc), _p(y), int(need_grad),
                                            _p(ws), ws.numel(), stream), "fcr_lstm_forward")
         if need_grad:
@@ -71,7 +71,7 @@ class LSTMFunction(torch.autograd.Function):
         lib = _native.load()
         _native.check(lib.fcr_lstm_backward(ctypes.byref(ctx.dims), ctypes.byref(w), _p(dyc), g_ih, g_hh, _p(g[7]),
                                             _p(g[8]), _p(g[0]) if ctx.needs_input_grad[0] else None, _p(ctx.ws),
-                                            ctx.ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                            ctx.ws.numel(), _native.stream(dev)),
                       "fcr_lstm_backward")
         return tuple(gi if need else None for gi, need in zip(g, ctx.needs_input_grad))
 
