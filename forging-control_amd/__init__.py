@@ -7,7 +7,7 @@ backward, as hand-written HIP kernels behind the C ABI in include/fcr.h.
 from . import _native, closed_loop, data, distributed, graphed, inference, launch, loss_terms, many, plant, rollout, supervised, surrogate
 from .functions import FNNModel, LSTMModel, MPCLoss, NeuralNetwork
 from .inference import controller_step, simulate_rollout, simulate_step, simulator_make_step
-from .plant import ForgingRK4, PressParams, forging_rk4
+from .plant import ForgingRK4, PressParams, fit_press, forging_rk4
 from .data import DeviceLoader, SequenceWindows
 from .closed_loop import ClosedLoop, ClosedLoopBank, FeasibilityRecovery
 from .graphed import CapturedStep
@@ -15,6 +15,6 @@ from .many import ControllerBank, zip_loaders
 from .loss_terms import LossTerms
 
 __all__ = ["FNNModel", "LSTMModel", "MPCLoss", "NeuralNetwork", "rollout", "distributed", "inference",
-           "simulate_step", "simulate_rollout", "controller_step", "simulator_make_step", "plant", "ForgingRK4", "forging_rk4", "PressParams",
+           "simulate_step", "simulate_rollout", "controller_step", "simulator_make_step", "plant", "ForgingRK4", "forging_rk4", "PressParams", "fit_press",
            "data", "SequenceWindows", "DeviceLoader", "surrogate", "closed_loop", "ClosedLoop", "ClosedLoopBank", "FeasibilityRecovery", "graphed",
            "CapturedStep", "launch", "supervised", "many", "ControllerBank", "zip_loaders", "loss_terms", "LossTerms", "_native"]

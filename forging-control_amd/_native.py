@@ -39,7 +39,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_closed_loop_run_bank", "fcr_press_nominal", "fcr_plant_rk4_press", "fcr_feasibility_project_press",
            "fcr_closed_loop_run_bank_press", "fcr_loss_terms_default", "fcr_forward_terms", "fcr_backward_terms",
            "fcr_forward_many_terms", "fcr_backward_many_terms", "fcr_plant_rk4_vjp", "fcr_closed_loop_vjp_workspace_size",
-           "fcr_closed_loop_vjp")
+           "fcr_closed_loop_vjp", "fcr_plant_rk4_vjp_press", "fcr_closed_loop_vjp_press",
+           "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -228,7 +229,7 @@ _SIGNATURES = (
     ("fcr_wide_bwd_cell", _i32, [_i32, _i32, _i32] + [_vp] * 11 + [_sz, _vp]),
 )
 # Pure additions to ABI 8 that an FCR_LIB development build may predate, each under the symbol load() probes for: the press
-# as data, the loss's terms as data, the differentiable press
+# as data, the loss's terms as data, the differentiable press, its gradients with respect to the press parameters
 _ADDITIONS = {
     "fcr_press_nominal": (
         ("fcr_press_nominal", None, [_press]),
@@ -247,6 +248,12 @@ _ADDITIONS = {
         ("fcr_plant_rk4_vjp", _i32, [_i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
         ("fcr_closed_loop_vjp_workspace_size", _i32, [_i32, _i32, _i32, _P(_sz)]),
         ("fcr_closed_loop_vjp", _i32, [_P(FcrClosedLoopGrad), _vp, _sz, _vp]),
+    ),
+    "fcr_plant_rk4_vjp_press": (
+        ("fcr_plant_rk4_vjp_press", _i32, [_i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+        ("fcr_closed_loop_vjp_press", _i32, [_P(FcrClosedLoopGrad), _vp, _vp, _sz, _vp]),
+        ("fcr_press_grad_sum_workspace_size", _i32, [_i32, _P(_sz)]),
+        ("fcr_press_grad_sum", _i32, [_i32, _vp, _vp, _vp, _sz, _vp]),
     ),
 }
 

@@ -31,7 +31,7 @@ import torch
 from . import _native
 from .functions import _controller_params
 from .inference import simulate_rollout
-from .plant import SUBSTEPS_REFERENCE, TS_REFERENCE, PressParams, as_press_table
+from .plant import SUBSTEPS_REFERENCE, TS_REFERENCE, PressParams, as_press_table, press_grad_sum
 
 
 def tvp_fun(t_now: float, ref_step: float, bias_work: int, bias_return: int, epsilon: float = 1e-7) -> float:
@@ -243,8 +243,16 @@ class ClosedLoop(_LoopConfig):
         and ``y_dot > 0``; valve-flow derivatives 0 at a zero pressure difference, branch by ``z >= 0``; friction slope
         ``FT/0.5`` where ``|y_dot| <= 0.5``, else 0; smooth floor ``0.5 (1 + p / sqrt(p^2 + eps))``. Raises ``ValueError``
         with ``process_noise``, ``meas_noise`` (the record ``x + v`` does not give the unperturbed state back exactly) or
-        ``feasibility`` (the projection is not differentiable). No gradient reaches ``ref`` or ``plant_params``.
-        Gradients through the press grow with T: back-propagation through hundreds of steps is the caller's risk."""
+        ``feasibility`` (the projection is not differentiable). No gradient reaches ``ref``. Gradients through the press
+        grow with T: back-propagation through hundreds of steps is the caller's risk.
+
+        Gradients reach the press too: a ``plant_params`` tensor, ``(28,)`` or ``(B,28)``, that requires
+        grad is part of the graph (``fcr_closed_loop_vjp_press``); its ``.grad`` has its shape, dtype and device, for a
+        ``(28,)`` row the fixed-order fp64 sum over the trajectories. The parameters follow the same conventions: the
+        deformation fields (``MU, K, W0, H0, B0, T_DEF, M0..M4``) receive gradient only where ``y > 0`` and ``y_dot > 0``;
+        ``CD, RHO, D, PS, PT`` receive 0 from a valve at a zero pressure difference, ``PS`` and ``PT`` by the branch
+        ``z >= 0``; ``FT`` receives ``y_dot / 0.5`` inside the knee and 1 outside. A :class:`~.plant.PressParams` is a
+        constant. :class:`ClosedLoopBank` has no adjoint."""
         if plant_params is None:
             plant_params = self.plant_params
         if differentiable:
@@ -305,10 +313,13 @@ class _ClosedLoopGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loop, x0, ref, plant_params, w_inp, b_inp, w_out):
+        if torch.is_tensor(plant_params):
+            plant_params = plant_params.detach()
         x, u = loop.run(x0, ref, plant_params=plant_params)
         dev = x.device
         ctx.loop = loop
         ctx.tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+        ctx.press_like = (plant_params.shape, plant_params.dtype) if torch.is_tensor(plant_params) else None
         ctx.like = tuple((t.shape, t.device, t.dtype) for t in (x0, w_inp, b_inp, w_out))
         ctx.save_for_backward(x, u, ref.to(torch.float64).contiguous(),
                               *(p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in (w_inp, b_inp, w_out)))
@@ -317,21 +328,25 @@ class _ClosedLoopGrad(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_x, g_u):
         x, u, ref, w_inp, b_inp, w_out = ctx.saved_tensors
-        g = loop_vjp(ctx.loop, x, u, ref, g_x, g_u, (w_inp, b_inp, w_out), ctx.tab)
+        press_grad = ctx.needs_input_grad[3]
+        g = loop_vjp(ctx.loop, x, u, ref, g_x, g_u, (w_inp, b_inp, w_out), ctx.tab, press_grad=press_grad)
         like = lambda t, to: t.reshape(to[0]).to(device=to[1], dtype=to[2])
         x0_, wi_, bi_, wo_ = ctx.like
-        return (None, like(g["g_x0"], x0_), None, None, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_),
+        g_params = g["g_press"].reshape(ctx.press_like[0]).to(ctx.press_like[1]) if press_grad else None
+        return (None, like(g["g_x0"], x0_), None, g_params, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_),
                 like(g["g_w_out"], wo_))
 
 
 def loop_vjp(loop: "ClosedLoop", x: torch.Tensor, u: torch.Tensor, ref: torch.Tensor, g_x: torch.Tensor, g_u: torch.Tensor,
-             weights=None, plant_params=None) -> dict:
+             weights=None, plant_params=None, press_grad: bool = False) -> dict:
     """The vector-Jacobian product of a noise-free :meth:`ClosedLoop.run` without recovery (``fcr_closed_loop_vjp``): from
     the stored ``x (B,T+1,5)``, ``u (B,T)``, the ``ref`` of that run and the incoming ``g_x``, ``g_u``, a dict of fp64
     tensors ``g_x0 (B,5)``, ``dv (B,T)`` (the gradient at the controller's clamped fp32 output), ``g_w_inp (H,3)``,
     ``g_b_inp (H)``, ``g_w_out (H)``. ``weights``: the controller's three parameters as the run read them (default:
-    ``loop.controller``'s now); ``plant_params``: the run's. This is what ``run(differentiable=True)`` calls in its
-    backward; conventions: there."""
+    ``loop.controller``'s now); ``plant_params``: the run's. ``press_grad=True`` (``fcr_closed_loop_vjp_press``) adds
+    ``g_press``, the gradient of the press's 28 fields in ``plant_params``' shape: ``(B,28)`` for a table, for one row
+    (a ``(28,)`` tensor, a :class:`~.plant.PressParams`, or ``None``: the reference's press) ``(28,)``, the fixed-order sum
+    over the trajectories. This is what ``run(differentiable=True)`` calls in its backward; conventions: there."""
     dev = x.device
     if dev.type != "cuda":
         raise RuntimeError(f"ClosedLoop runs on a ROCm device only (x on {x.device})")
@@ -344,6 +359,8 @@ def loop_vjp(loop: "ClosedLoop", x: torch.Tensor, u: torch.Tensor, ref: torch.Te
     x, u, ref, gx, gu = f64(x), f64(u), f64(ref), f64(g_x), f64(g_u)
     w_inp, b_inp, w_out = (t.detach().to(device=dev, dtype=torch.float32).contiguous()
                            for t in (_controller_params(loop.controller) if weights is None else weights))
+    if plant_params is None and press_grad:
+        plant_params = PressParams()
     tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
     if tab is not None and tuple(tab.shape) not in ((28,), (B, 28)):
         raise ValueError(f"plant_params must be a PressParams, (28,) or (B,28) with B = {B}, got shape {tuple(tab.shape)}")
@@ -360,6 +377,12 @@ def loop_vjp(loop: "ClosedLoop", x: torch.Tensor, u: torch.Tensor, ref: torch.Te
         (ctypes.c_double * 2)(*loop.in_scale), loop.ref_scale, loop.out_scale, p(x), p(u), p(gx), p(gu),
         None if tab is None else p(tab), 28 if tab is not None and tab.dim() == 2 else 0,
         p(out["g_x0"]), p(out["dv"]), p(out["g_w_inp"]), p(out["g_b_inp"]), p(out["g_w_out"]))
+    if press_grad:
+        g_press = new(B, 28)
+        _native.check(lib.fcr_closed_loop_vjp_press(ctypes.byref(args), ctypes.c_void_p(p(g_press)), ctypes.c_void_p(p(ws)),
+                                                    ws.numel(), _native.stream(dev)), "fcr_closed_loop_vjp_press")
+        out["g_press"] = g_press if tab.dim() == 2 else press_grad_sum(g_press)
+        return out
     _native.check(lib.fcr_closed_loop_vjp(ctypes.byref(args), ctypes.c_void_p(p(ws)), ws.numel(), _native.stream(dev)),
                   "fcr_closed_loop_vjp")
     return out

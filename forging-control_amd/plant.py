@@ -141,13 +141,41 @@ def forging_rk4(x0: torch.Tensor, u: torch.Tensor, ts: float = TS_REFERENCE,
     and ``y_dot > 0`` (at ``y_dot == 0`` its slope is infinite and is taken as 0, so a press at rest has finite
     gradients); the valve flow ``q = c z sign(a) sqrt(k|a|)`` has ``dq/da = dq/dz = 0`` at ``a == 0``, its branch chosen by
     ``z >= 0`` as in the forward; the friction's slope is ``FT/0.5`` where ``|y_dot| <= 0.5`` and 0 elsewhere; the smooth
-    pressure floor's is ``0.5 (1 + p / sqrt(p^2 + eps))``. No gradient reaches ``params``. Gradients through this plant
-    grow with S: back-propagation through hundreds of steps is the caller's risk."""
+    pressure floor's is ``0.5 (1 + p / sqrt(p^2 + eps))``. Gradients through this plant grow with S:
+    back-propagation through hundreds of steps is the caller's risk.
+
+    Gradients reach the press as well: when ``params`` is a ``(28,)`` or ``(B, 28)`` tensor that requires
+    grad, the result is attached to it and the backward runs the adjoint's parameter-gradient kernels
+    (``fcr_plant_rk4_vjp_press``); ``params.grad`` has the tensor's shape, dtype and device, for a ``(28,)`` row the sum
+    over the trajectories, added in fp64 in a fixed order (``fcr_press_grad_sum``: two backward calls give the same
+    bits). The same conventions hold for the parameters: the deformation fields (``MU, K, W0, H0, B0, T_DEF, M0..M4``)
+    receive gradient only where ``y > 0`` and ``y_dot > 0``; ``CD, RHO, D, PS, PT`` receive 0 from a valve at a zero
+    pressure difference, ``PS`` and ``PT`` by the branch ``z >= 0``; ``FT`` receives ``y_dot / 0.5`` inside the knee and
+    1 outside. A :class:`PressParams` is a constant, and with ``params`` not requiring grad the call is what it was."""
     if u.dim() == 1:
         u = u.unsqueeze(1)
-    if torch.is_grad_enabled() and (x0.requires_grad or u.requires_grad):
+    if torch.is_grad_enabled() and (x0.requires_grad or u.requires_grad or _wants_grad(params)):
         return _ForgingRK4Grad.apply(x0, u, float(ts), int(substeps), bool(smooth), params)
     return _forging_rk4(x0, u, ts, substeps, smooth, params)[0]
+
+
+def _wants_grad(params) -> bool:
+    """Whether ``params`` is a tensor the graph follows (a PressParams, an array or None is a constant)."""
+    return torch.is_tensor(params) and params.requires_grad
+
+
+def press_grad_sum(g_press: torch.Tensor) -> torch.Tensor:
+    """``(28,)`` fp64: the sum over the trajectories of ``g_press (B, 28)``, in a fixed order (``fcr_press_grad_sum``)."""
+    B, dev = g_press.shape[0], g_press.device
+    lib = _native.load()
+    size = ctypes.c_size_t(0)
+    _native.check(lib.fcr_press_grad_sum_workspace_size(B, ctypes.byref(size)), "fcr_press_grad_sum_workspace_size")
+    ws = torch.empty(max(size.value, 8), dtype=torch.uint8, device=dev)
+    g_row = torch.empty(28, dtype=torch.float64, device=dev)
+    _native.check(lib.fcr_press_grad_sum(B, ctypes.c_void_p(g_press.data_ptr()), ctypes.c_void_p(g_row.data_ptr()),
+                                         ctypes.c_void_p(ws.data_ptr()), ws.numel(), _native.stream(dev)),
+                  "fcr_press_grad_sum")
+    return g_row
 
 
 def _forging_rk4(x0, u, ts, substeps, smooth, params):
@@ -176,13 +204,14 @@ def _forging_rk4(x0, u, ts, substeps, smooth, params):
 
 class _ForgingRK4Grad(torch.autograd.Function):
     """:func:`forging_rk4` attached to the graph: the forward is the plain launch, the backward ``fcr_plant_rk4_vjp`` on
-    the stored states and commands."""
+    the stored states and commands (``fcr_plant_rk4_vjp_press`` when the parameter tensor asks for its gradient)."""
 
     @staticmethod
     def forward(ctx, x0, u, ts, substeps, smooth, params):
-        x, uc, tab = _forging_rk4(x0, u, ts, substeps, smooth, params)
+        x, uc, tab = _forging_rk4(x0, u, ts, substeps, smooth, params.detach() if torch.is_tensor(params) else params)
         ctx.save_for_backward(x, uc)
         ctx.tab, ctx.step, ctx.dtypes = tab, (ts, substeps, smooth), (x0.dtype, u.dtype)
+        ctx.params_dtype = params.dtype if torch.is_tensor(params) else None
         return x
 
     @staticmethod
@@ -194,13 +223,18 @@ class _ForgingRK4Grad(torch.autograd.Function):
         g_x0 = torch.empty(B, 5, dtype=torch.float64, device=x.device)
         g_u = torch.empty(B, S, dtype=torch.float64, device=x.device)
         tab = ctx.tab
-        _native.check(_native.load().fcr_plant_rk4_vjp(
+        name, extra, g_params = "fcr_plant_rk4_vjp", (), None
+        if ctx.needs_input_grad[5]:
+            g_press = torch.empty(B, 28, dtype=torch.float64, device=x.device)
+            name, extra = "fcr_plant_rk4_vjp_press", (ctypes.c_void_p(g_press.data_ptr()),)
+        _native.check(getattr(_native.load(), name)(
             B, S, ts, substeps, int(smooth), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(uc.data_ptr()),
             ctypes.c_void_p(g.data_ptr()), None if tab is None else ctypes.c_void_p(tab.data_ptr()),
             28 if tab is not None and tab.dim() == 2 else 0, ctypes.c_void_p(g_x0.data_ptr()),
-            ctypes.c_void_p(g_u.data_ptr()), _native.stream(x.device)),
-            "fcr_plant_rk4_vjp")
-        return g_x0.to(ctx.dtypes[0]), g_u.to(ctx.dtypes[1]), None, None, None, None
+            ctypes.c_void_p(g_u.data_ptr()), *extra, _native.stream(x.device)), name)
+        if extra:
+            g_params = (g_press if tab.dim() == 2 else press_grad_sum(g_press)).to(ctx.params_dtype)
+        return g_x0.to(ctx.dtypes[0]), g_u.to(ctx.dtypes[1]), None, None, None, g_params
 
 
 class ForgingRK4:
@@ -218,3 +252,65 @@ class ForgingRK4:
     def rollout(self, x0: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
         """All S+1 states of the trajectories under commands u (B, S)."""
         return forging_rk4(x0, u, self.TS, self.substeps, self.smooth, self.params)
+
+
+def fit_press(x_obs: torch.Tensor, u: torch.Tensor, fields, init: PressParams = PressParams(), ts: float = TS_REFERENCE,
+              substeps: int = SUBSTEPS_REFERENCE, smooth: bool = False, max_iter: int = 60):
+    """Fit ONE press, shared by all B trajectories, to recorded states ``x_obs (B, S+1, 5)`` under the recorded commands
+    ``u (B, S)``: ``(PressParams, info)``.
+
+    Single shooting from ``x_obs[:, 0]``: the unknowns are the log-multipliers q of the named ``fields`` (field =
+    ``init``'s value times ``exp(q)``, so a :attr:`PressParams.POSITIVE` field stays positive; every other field keeps
+    ``init``'s value), the loss is ``mean(((x - x_obs) / scale)^2)`` with ``x = forging_rk4(x_obs[:, 0], u, params=row)``
+    and ``scale`` the per-state maximum of ``|x_obs|``, its gradient is :func:`forging_rk4`'s parameter gradient, and the
+    optimiser is one ``step`` of ``torch.optim.LBFGS(lr=1, max_iter=max_iter, history_size=10,
+    line_search_fn="strong_wolfe", tolerance_grad=1e-14, tolerance_change=1e-16)``. ``info``: ``loss0`` (at ``init``),
+    ``loss`` (at the result), ``evals`` (loss + gradient evaluations) and ``multipliers`` (field -> ``exp(q)``).
+
+    Which fields a trace can identify is the caller's business: a field the trace is insensitive to is NOT recovered —
+    ``B_DAMP``, whose sensitivity on the reference's traces is three orders below ``CD``'s, ``M0``'s or ``KB``'s, stays
+    where it started when fitted beside them — and fields that enter only through one coefficient (``CD`` and ``D``,
+    ``M1`` and ``T_DEF``) cannot be told apart. Gradients through the press grow with S: a trace of
+    hundreds of steps is the caller's risk; cut it into shorter ones. Runs on a ROCm device only."""
+    fields = tuple(fields)
+    unknown = [f for f in fields if f not in PressParams.NAMES]
+    if unknown or not fields or len(set(fields)) != len(fields):
+        raise ValueError(f"fit_press: fields must be distinct names of {PressParams.NAMES}, got {fields}")
+    if not torch.is_tensor(x_obs) or not torch.is_tensor(u) or x_obs.device.type != "cuda" or u.device != x_obs.device:
+        raise RuntimeError("fit_press runs on a ROCm device only (x_obs on "
+                           f"{getattr(x_obs, 'device', 'the host')}, u on {getattr(u, 'device', 'the host')})")
+    if u.dim() != 2 or x_obs.dim() != 3 or tuple(x_obs.shape) != (u.shape[0], u.shape[1] + 1, 5):
+        raise ValueError(f"fit_press: x_obs must be (B, S+1, 5) and u (B, S); got {tuple(x_obs.shape)}, {tuple(u.shape)}")
+    dev = x_obs.device
+    x_obs, u = x_obs.detach().to(torch.float64), u.detach().to(torch.float64)
+    x0 = x_obs[:, 0].contiguous()
+    scale = x_obs.abs().amax((0, 1)).clamp_min(torch.finfo(torch.float64).tiny)
+    base = torch.tensor(init.as_row(), dtype=torch.float64, device=dev)
+    index = torch.tensor([PressParams.NAMES.index(f) for f in fields], device=dev)
+    q = torch.zeros(len(fields), dtype=torch.float64, device=dev, requires_grad=True)
+
+    def loss_of(q):
+        row = base.index_put((index,), base[index] * torch.exp(q))
+        x = forging_rk4(x0, u, ts, substeps, smooth, params=row)
+        return (((x - x_obs) / scale) ** 2).mean()
+
+    opt = torch.optim.LBFGS([q], lr=1, max_iter=int(max_iter), history_size=10, line_search_fn="strong_wolfe",
+                            tolerance_grad=1e-14, tolerance_change=1e-16)
+    evals = 0
+
+    def closure():
+        nonlocal evals
+        evals += 1
+        opt.zero_grad()
+        loss = loss_of(q)
+        loss.backward()
+        return loss
+
+    with torch.no_grad():
+        loss0 = float(loss_of(q))
+    opt.step(closure)
+    with torch.no_grad():
+        loss = float(loss_of(q))
+        mult = torch.exp(q).cpu().tolist()
+    fitted = init.replace(**{f: getattr(init, f) * m for f, m in zip(fields, mult)})
+    return fitted, {"loss0": loss0, "loss": loss, "evals": evals, "multipliers": dict(zip(fields, mult))}

@@ -455,7 +455,8 @@ int fcr_closed_loop_run_bank_press(const fcr_closed_loop_bank *args, const doubl
  * where |y_dot| <= 0.5 and 0 elsewhere; the smooth pressure floor's is 0.5 (1 + p / sqrt(p^2 + eps)). The controller's
  * fp32 chain is recomputed from the stored record in the forward's operation order, so its ReLU masks (ReLU'(0) = 0) and
  * Hardtanh mask (1 only for -1 < v < 1) are the forward's; float casts are differentiated as the identity.
- * Not covered: process / measurement noise, feasibility recovery, gradients with respect to the press parameters.
+ * Not covered: process / measurement noise, feasibility recovery. (Gradients with respect to the press parameters: the
+ * *_press calls below.)
  */
 int fcr_plant_rk4_vjp(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x, const double *u,
                       const double *g_x, const double *press, int64_t stride_traj, double *g_x0, double *g_u,
@@ -480,6 +481,28 @@ typedef struct fcr_closed_loop_grad {
 
 int fcr_closed_loop_vjp_workspace_size(int32_t B, int32_t T, int32_t ctrl_hidden, size_t *bytes);
 int fcr_closed_loop_vjp(const fcr_closed_loop_grad *args, void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * Gradients with respect to the press (a pure addition to ABI 8): the two calls above, which compute
+ * what they compute there, and beside it g_press (B,28) = dL/d(the 28 fields of each trajectory's row, fcr_press's
+ * order) — per trajectory whatever the stride: under stride_traj = 0 row b holds trajectory b's share of the shared
+ * row's gradient, which fcr_press_grad_sum adds up. press is required (the reference's literals have no gradient).
+ * The parameter terms are collected along the same reverse recursion, each right-hand side's (df/dc)^T a over the
+ * coefficients derive() forms, then carried to the row through derive()'s Jacobian. Conventions as above: the eleven
+ * deformation fields (mu, k, w0, h0, b0, t_def, m0..m4) receive gradient only where y > 0 && y_dot > 0; cd, rho, d, ps
+ * and pt receive 0 from a valve at a zero pressure difference, ps and pt by the branch z >= 0 as in the forward; ft
+ * receives y_dot / 0.5 inside the knee and 1 outside. S = 0 / T = 0: g_press = 0. B = 0 is a no-op.
+ *
+ *   fcr_press_grad_sum: g_row (28) = sum over b of g_press (B,28), in fp64 and in a fixed order (blocks of 256
+ *     trajectories added in order, then the blocks in order; no atomics: the same call twice gives the same bits).
+ *     ws: device scratch of fcr_press_grad_sum_workspace_size bytes. B = 0: g_row = 0 (where given).
+ */
+int fcr_plant_rk4_vjp_press(int32_t B, int32_t S, double ts, int32_t substeps, int32_t smooth, const double *x,
+                            const double *u, const double *g_x, const double *press, int64_t stride_traj, double *g_x0,
+                            double *g_u, double *g_press, void *stream);
+int fcr_closed_loop_vjp_press(const fcr_closed_loop_grad *args, double *g_press, void *ws, size_t ws_bytes, void *stream);
+int fcr_press_grad_sum_workspace_size(int32_t B, size_t *bytes);
+int fcr_press_grad_sum(int32_t B, const double *g_press, double *g_row, void *ws, size_t ws_bytes, void *stream);
 
 /*
  * Training-sample windows: the tables of the concatenated per-trajectory
