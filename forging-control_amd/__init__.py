@@ -13,8 +13,10 @@ from .closed_loop import ClosedLoop, ClosedLoopBank, FeasibilityRecovery
 from .graphed import CapturedStep
 from .many import ControllerBank, zip_loaders
 from .loss_terms import LossTerms
+from . import press_loss
+from .press_loss import PressLoss, train_on_press
 
-__all__ = ["FNNModel", "LSTMModel", "MPCLoss", "NeuralNetwork", "rollout", "distributed", "inference",
+__all__ = ["press_loss", "PressLoss", "train_on_press","FNNModel", "LSTMModel", "MPCLoss", "NeuralNetwork", "rollout", "distributed", "inference",
            "simulate_step", "simulate_rollout", "controller_step", "simulator_make_step", "plant", "ForgingRK4", "forging_rk4", "PressParams", "fit_press",
            "data", "SequenceWindows", "DeviceLoader", "surrogate", "closed_loop", "ClosedLoop", "ClosedLoopBank", "FeasibilityRecovery", "graphed",
            "CapturedStep", "launch", "supervised", "many", "ControllerBank", "zip_loaders", "loss_terms", "LossTerms", "_native"]

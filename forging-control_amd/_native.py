@@ -40,7 +40,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_closed_loop_run_bank_press", "fcr_loss_terms_default", "fcr_forward_terms", "fcr_backward_terms",
            "fcr_forward_many_terms", "fcr_backward_many_terms", "fcr_plant_rk4_vjp", "fcr_closed_loop_vjp_workspace_size",
            "fcr_closed_loop_vjp", "fcr_plant_rk4_vjp_press", "fcr_closed_loop_vjp_press",
-           "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum")
+           "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum", "fcr_closed_loop_bank_vjp_workspace_size",
+           "fcr_closed_loop_bank_vjp", "fcr_closed_loop_bank_loss_vjp")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -176,6 +177,32 @@ class FcrClosedLoopGrad(ctypes.Structure):
     ]
 
 
+class FcrClosedLoopBankGrad(ctypes.Structure):
+    """fcr_closed_loop_bank_grad (include/fcr.h): the stored run of M stacked controllers and where its adjoint goes."""
+    _fields_ = [
+        ("n_models", ctypes.c_int32), ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("ts", ctypes.c_double),
+        ("substeps", ctypes.c_int32), ("smooth", ctypes.c_int32), ("ref", ctypes.c_void_p), ("ref_stride", ctypes.c_int64),
+        ("ctrl_w_inp", ctypes.c_void_p), ("ctrl_b_inp", ctypes.c_void_p), ("ctrl_w_out", ctypes.c_void_p),
+        ("ctrl_hidden", ctypes.c_int32), ("in_scale", ctypes.c_double * 2),
+        ("ref_scale", ctypes.c_double), ("out_scale", ctypes.c_double),
+        ("x", ctypes.c_void_p), ("u", ctypes.c_void_p),
+        ("press", ctypes.c_void_p), ("stride_model", ctypes.c_int64), ("stride_traj", ctypes.c_int64),
+        ("truncate", ctypes.c_int32),
+        ("g_x0", ctypes.c_void_p), ("dv", ctypes.c_void_p),                                          # (M,B,5) or NULL, (M,B,T)
+        ("g_w_inp", ctypes.c_void_p), ("g_b_inp", ctypes.c_void_p), ("g_w_out", ctypes.c_void_p),   # fp64, stacked
+    ]
+
+
+class FcrPressLoss(ctypes.Structure):
+    """fcr_press_loss (include/fcr.h): the MPC loss on the press record — the terms table (device) and its host copy, the
+    pressure scales, u_prev, and where cost (M,B) and loss (M) go."""
+    _fields_ = [
+        ("terms", ctypes.c_void_p), ("terms_stride", ctypes.c_int64), ("terms_host", ctypes.POINTER(ctypes.c_double)),
+        ("p_scale", ctypes.c_double * 2), ("u_prev", ctypes.c_void_p), ("u_prev_stride", ctypes.c_int64),
+        ("value_only", ctypes.c_int32), ("cost", ctypes.c_void_p), ("loss", ctypes.c_void_p),
+    ]
+
+
 class FcrSupervised(ctypes.Structure):
     """fcr_supervised (include/fcr.h): one epoch of the supervised baseline for n_models stacked FNNModels."""
     _fields_ = [
@@ -254,6 +281,11 @@ _ADDITIONS = {
         ("fcr_closed_loop_vjp_press", _i32, [_P(FcrClosedLoopGrad), _vp, _vp, _sz, _vp]),
         ("fcr_press_grad_sum_workspace_size", _i32, [_i32, _P(_sz)]),
         ("fcr_press_grad_sum", _i32, [_i32, _vp, _vp, _vp, _sz, _vp]),
+    ),
+    "fcr_closed_loop_bank_vjp": (                            # training a bank on the press
+        ("fcr_closed_loop_bank_vjp_workspace_size", _i32, [_i32, _i32, _i32, _i32, _P(_sz)]),
+        ("fcr_closed_loop_bank_vjp", _i32, [_P(FcrClosedLoopBankGrad), _vp, _vp, _vp, _sz, _vp]),
+        ("fcr_closed_loop_bank_loss_vjp", _i32, [_P(FcrClosedLoopBankGrad), _P(FcrPressLoss), _vp, _sz, _vp]),
     ),
 }
 

@@ -252,7 +252,8 @@ class ClosedLoop(_LoopConfig):
         deformation fields (``MU, K, W0, H0, B0, T_DEF, M0..M4``) receive gradient only where ``y > 0`` and ``y_dot > 0``;
         ``CD, RHO, D, PS, PT`` receive 0 from a valve at a zero pressure difference, ``PS`` and ``PT`` by the branch
         ``z >= 0``; ``FT`` receives ``y_dot / 0.5`` inside the knee and 1 outside. A :class:`~.plant.PressParams` is a
-        constant. :class:`ClosedLoopBank` has no adjoint."""
+        constant. :class:`ClosedLoopBank` has its own adjoint for M models in one launch, without the press's gradients
+        (``ClosedLoopBank.run(differentiable=True)``)."""
         if plant_params is None:
             plant_params = self.plant_params
         if differentiable:
@@ -459,7 +460,7 @@ class ClosedLoopBank(_LoopConfig):
 
     def run(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
             meas_noise: torch.Tensor | None = None, feasibility: FeasibilityRecovery | None = None, store: bool = True,
-            p_bounds=None, plant_params=None):
+            p_bounds=None, plant_params=None, differentiable: bool = False):
         """``x0 (B,5)`` or ``(M,B,5)``, ``ref (B,T)`` or ``(M,B,T)``, each noise ``(B,T,5)`` or ``(M,B,T,5)``: without
         the leading M one copy is shared by all models (and read once from memory, not expanded). ``p_bounds``:
         ``((p1_lo, p1_hi), (p2_lo, p2_hi))`` in Pa for the violation statistics; default the ``feasibility``'s own
@@ -471,7 +472,26 @@ class ClosedLoopBank(_LoopConfig):
         lie, through zero strides, not expanded. The projection of ``feasibility`` integrates that object's
         ``model_params`` (default: the reference's press), one set for the launch — plant and model need not agree, which
         is what the violation statistics then measure. ``None`` (and no ``model_params``) is the call as it always was:
-        ``fcr_closed_loop_run_bank`` and its kernels; otherwise ``fcr_closed_loop_run_bank_press``."""
+        ``fcr_closed_loop_run_bank`` and its kernels; otherwise ``fcr_closed_loop_run_bank_press``.
+
+        ``differentiable=True``: ``x`` and ``u`` of the returned dict are attached to the bank's
+        stacked ``w_inp``, ``b_inp``, ``w_out`` and to ``x0`` (a shared ``(B,5)`` ``x0`` receives the sum over the
+        models); under ``torch.no_grad()`` they come back detached. The forward is the launch above, same bits; the
+        backward is the bank's adjoint in one launch (``fcr_closed_loop_bank_vjp``, :func:`bank_vjp`) with
+        :meth:`ClosedLoop.run`'s conventions. ``plant_params`` is taken in every form, as constants. Raises
+        ``ValueError`` with noise, ``feasibility`` or ``store=False``. Every other entry of the dict is detached."""
+        if differentiable:
+            given = {"process_noise": process_noise, "meas_noise": meas_noise, "feasibility": feasibility,
+                     "store=False": None if store else False}
+            for name, v in given.items():
+                if v is not None:
+                    raise ValueError(f"ClosedLoopBank.run(differentiable=True) does not take {name}: the adjoint covers "
+                                     "the stored noise-free loop without recovery (DESIGN.md §7.13, §7.16)")
+            if torch.is_grad_enabled():
+                holder = {}
+                x, u = _ClosedLoopBankGrad.apply(self, holder, p_bounds, x0, ref, plant_params, self.bank.w_inp,
+                                                 self.bank.b_inp, self.bank.w_out)
+                return {**holder["out"], "x": x, "u": u}
         M = self.bank.w_inp.shape[0]
         dev, B, T, stacked, out, prefix, keep = self._prepare(M, (self.bank.w_inp, self.bank.b_inp, self.bank.w_out), x0, ref,
                                                               process_noise, meas_noise, feasibility, store)
@@ -532,3 +552,131 @@ class ClosedLoopBank(_LoopConfig):
         track = track.reshape(M, B, T + 1, 4)
         results_lstm = {"y_dot": track[..., 0], "p1": track[..., 1], "p2": track[..., 2], "z": track[..., 3]}
         return results, results_lstm
+
+
+class _ClosedLoopBankGrad(torch.autograd.Function):
+    """:meth:`ClosedLoopBank.run` attached to the graph: the forward is the plain launch, the backward
+    ``fcr_closed_loop_bank_vjp`` on the stored run. ``holder['out']`` receives the run's whole dict."""
+
+    @staticmethod
+    def forward(ctx, loop, holder, p_bounds, x0, ref, plant_params, w_inp, b_inp, w_out):
+        if torch.is_tensor(plant_params):
+            plant_params = plant_params.detach()
+        out = loop.run(x0, ref, p_bounds=p_bounds, plant_params=plant_params)
+        holder["out"] = dict(out)
+        x, u = out["x"], out["u"]
+        dev = x.device
+        ctx.loop = loop
+        ctx.tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+        ctx.like = tuple((t.shape, t.device, t.dtype) for t in (x0, w_inp, b_inp, w_out))
+        ctx.save_for_backward(x, u, ref.to(torch.float64).contiguous(),
+                              *(p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in (w_inp, b_inp, w_out)))
+        return x, u
+
+    @staticmethod
+    def backward(ctx, g_x, g_u):
+        x, u, ref, w_inp, b_inp, w_out = ctx.saved_tensors
+        g = bank_vjp(ctx.loop, x, u, ref, g_x, g_u, (w_inp, b_inp, w_out), ctx.tab, want_x0=ctx.needs_input_grad[3])
+        like = lambda t, to: t.reshape(to[0]).to(device=to[1], dtype=to[2])
+        x0_, wi_, bi_, wo_ = ctx.like
+        g_x0 = None
+        if ctx.needs_input_grad[3]:
+            g_x0 = like(g["g_x0"] if len(x0_[0]) == 3 else g["g_x0"].sum(0), x0_)   # a shared x0: the sum over the models
+        return (None, None, None, g_x0, None, None, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_), like(g["g_w_out"], wo_))
+
+
+def _bank_adjoint(who, loop, x, u, ref, weights, plant_params, truncate, want_x0, want_grads=True):
+    """What :func:`bank_vjp` and :func:`bank_loss_vjp` share: the checks, the conversions, the outputs, the workspace and
+    the ``fcr_closed_loop_bank_grad`` of the call. Returns ``(args, out, ws, keep)``."""
+    dev = x.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"ClosedLoopBank runs on a ROCm device only (x on {x.device})")
+    if u.dim() != 3 or tuple(x.shape) != (*u.shape[:2], u.shape[2] + 1, 5):
+        raise ValueError(f"{who}: x must be (M,B,T+1,5) and u (M,B,T); got {tuple(x.shape)}, {tuple(u.shape)}")
+    M, B, T = u.shape
+    if tuple(ref.shape) not in ((B, T), (M, B, T)):
+        raise ValueError(f"{who}: ref must be (B,T) = {(B, T)} or (M,B,T) = {(M, B, T)}, got {tuple(ref.shape)}")
+    if int(truncate) < 0:
+        raise ValueError(f"{who}: truncate = {truncate} must be >= 0 (0 = none)")
+    f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
+    x, u, ref = f64(x), f64(u), f64(ref)
+    if weights is None:
+        weights = (loop.bank.w_inp, loop.bank.b_inp, loop.bank.w_out)
+    w_inp, b_inp, w_out = (t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in weights)
+    H = w_inp.shape[-2]
+    if tuple(w_inp.shape) != (M, H, 3) or tuple(b_inp.shape) != (M, H) or tuple(w_out.shape) != (M, H):
+        raise ValueError(f"{who}: the bank's parameters must be (M,H,3), (M,H), (M,H) with M = {M}; got "
+                         f"{tuple(w_inp.shape)}, {tuple(b_inp.shape)}, {tuple(w_out.shape)}")
+    tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+    if tab is not None and tuple(tab.shape) not in ((28,), (B, 28), (M, B, 28)):
+        raise ValueError(f"plant_params must be a PressParams, (28,), (B,28) = {(B, 28)} or (M,B,28) = {(M, B, 28)}, "
+                         f"got shape {tuple(tab.shape)}")
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+    out = {}
+    if want_grads:
+        out = {"g_x0": new(M, B, 5) if want_x0 else None, "dv": new(M, B, T), "g_w_inp": new(M, H, 3),
+               "g_b_inp": new(M, H), "g_w_out": new(M, H)}
+    lib = _native.load()
+    size = ctypes.c_size_t(0)
+    _native.check(lib.fcr_closed_loop_bank_vjp_workspace_size(M, B, T, H, ctypes.byref(size)),
+                  "fcr_closed_loop_bank_vjp_workspace_size")
+    ws = torch.empty(max(size.value, 8), dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else t.data_ptr()
+    args = _native.FcrClosedLoopBankGrad(
+        M, B, T, loop.ts, loop.substeps, int(loop.smooth), p(ref), B * T if ref.dim() == 3 else 0, p(w_inp), p(b_inp),
+        p(w_out), H, (ctypes.c_double * 2)(*loop.in_scale), loop.ref_scale, loop.out_scale, p(x), p(u), p(tab),
+        B * 28 if tab is not None and tab.dim() == 3 else 0, 28 if tab is not None and tab.dim() >= 2 else 0,
+        int(truncate), p(out.get("g_x0")), p(out.get("dv")), p(out.get("g_w_inp")), p(out.get("g_b_inp")),
+        p(out.get("g_w_out")))
+    return args, out, ws, (x, u, ref, w_inp, b_inp, w_out, tab)
+
+
+def bank_vjp(loop: "ClosedLoopBank", x, u, ref, g_x, g_u, weights=None, plant_params=None, truncate: int = 0,
+             want_x0: bool = True) -> dict:
+    """:func:`loop_vjp` for the M models of a :class:`ClosedLoopBank` in one reverse launch (``fcr_closed_loop_bank_vjp``):
+    from the stored ``x (M,B,T+1,5)``, ``u (M,B,T)``, the run's ``ref`` (``(B,T)`` shared or ``(M,B,T)``) and the incoming
+    ``g_x``, ``g_u`` of those shapes, a dict of fp64 tensors ``g_x0 (M,B,5)`` (``None`` with ``want_x0=False``),
+    ``dv (M,B,T)``, ``g_w_inp (M,H,3)``, ``g_b_inp (M,H)``, ``g_w_out (M,H)`` — model m's are :func:`loop_vjp`'s for that
+    model alone. ``weights``: the bank's three stacked parameters as the run read them (default: the bank's now);
+    ``plant_params``: the run's, in any of its four forms. ``truncate = K > 0``: the states at ``t = K, 2K, ... < T``
+    count as constants for the step that starts from them (``x = x.detach()`` there)."""
+    args, out, ws, keep = _bank_adjoint("bank_vjp", loop, x, u, ref, weights, plant_params, truncate, want_x0)
+    dev, (M, B, T) = keep[0].device, keep[1].shape
+    if tuple(g_x.shape) != (M, B, T + 1, 5) or tuple(g_u.shape) != (M, B, T):
+        raise ValueError(f"bank_vjp: g_x must be (M,B,T+1,5) and g_u (M,B,T); got {tuple(g_x.shape)}, {tuple(g_u.shape)}")
+    gx, gu = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (g_x, g_u))
+    _native.check(_native.load().fcr_closed_loop_bank_vjp(
+        ctypes.byref(args), ctypes.c_void_p(gx.data_ptr()), ctypes.c_void_p(gu.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+        ws.numel(), _native.stream(dev)), "fcr_closed_loop_bank_vjp")
+    return out
+
+
+def bank_loss_vjp(loop: "ClosedLoopBank", x, u, ref, terms_rows, p_scale, u_prev=None, weights=None, plant_params=None,
+                  truncate: int = 0, want_x0: bool = True, value_only: bool = False) -> dict:
+    """The MPC loss on the stored run of a bank and its gradient in one reverse launch
+    (``fcr_closed_loop_bank_loss_vjp``; the loss: :class:`~.press_loss.PressLoss`). ``terms_rows``: one row
+    ``(alpha, p1_lo, p1_hi, p2_lo, p2_hi, weight)`` for all models or one per model; ``p_scale``: the two pressure
+    scales; ``u_prev``: ``(B,)`` shared or ``(M,B)``, or ``None``. Returns :func:`bank_vjp`'s dict and ``cost (M,B)``,
+    ``loss (M,)``; ``value_only=True``: those two alone, nothing is differentiated."""
+    args, out, ws, keep = _bank_adjoint("bank_loss_vjp", loop, x, u, ref, weights, plant_params, truncate, want_x0,
+                                        want_grads=not value_only)
+    dev, (M, B, T) = keep[0].device, keep[1].shape
+    rows = np.ascontiguousarray(np.asarray(terms_rows, dtype=np.float64).reshape(-1, 6))
+    if rows.shape[0] not in (1, M):
+        raise ValueError(f"bank_loss_vjp: {rows.shape[0]} terms rows for a bank of {M} models")
+    table = torch.tensor(rows, dtype=torch.float64, device=dev)
+    if u_prev is not None:
+        if tuple(u_prev.shape) not in ((B,), (M, B)):
+            raise ValueError(f"bank_loss_vjp: u_prev must be (B,) = {(B,)} or (M,B) = {(M, B)}, got {tuple(u_prev.shape)}")
+        u_prev = u_prev.detach().to(device=dev, dtype=torch.float64).contiguous()
+    out["cost"] = torch.zeros(M, B, dtype=torch.float64, device=dev)
+    out["loss"] = torch.zeros(M, dtype=torch.float64, device=dev)
+    loss = _native.FcrPressLoss(
+        table.data_ptr(), 6 if rows.shape[0] > 1 else 0, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        (ctypes.c_double * 2)(float(p_scale[0]), float(p_scale[1])), None if u_prev is None else u_prev.data_ptr(),
+        B if u_prev is not None and u_prev.dim() == 2 else 0, int(bool(value_only)), out["cost"].data_ptr(),
+        out["loss"].data_ptr())
+    _native.check(_native.load().fcr_closed_loop_bank_loss_vjp(
+        ctypes.byref(args), ctypes.byref(loss), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _native.stream(dev)),
+        "fcr_closed_loop_bank_loss_vjp")
+    return out

@@ -505,6 +505,72 @@ int fcr_press_grad_sum_workspace_size(int32_t B, size_t *bytes);
 int fcr_press_grad_sum(int32_t B, const double *g_press, double *g_row, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * Training a bank of controllers on the press (a pure addition to ABI 8): the adjoint of the noise-free
+ * closed loop without recovery for n_models controllers in ONE reverse launch on the record fcr_closed_loop_run_bank /
+ * _bank_press stored, then the parameter gradients of all models in one launch and one reduction.
+ *
+ * fcr_closed_loop_bank_grad: fcr_closed_loop_grad's fields for the stacked models. ctrl_w_inp (M,hidden,3), ctrl_b_inp
+ * and ctrl_w_out (M,hidden); x (M,B,T+1,5), u (M,B,T); model m reads its references from ref + m * ref_stride ELEMENTS
+ * (0: one (B,T) shared, else >= B*T) and trajectory b of model m the press row press + m * stride_model + b * stride_traj
+ * (NULL: the reference's press, both strides 0), as the forward did. truncate = K > 0 is truncated back-propagation:
+ * the states x_t at t = K, 2K, ... < T count as constants for the step (controller included) that starts from them,
+ * while the direct terms on x_t and u_{t-1} still reach the step that produced them; 0 = none.
+ * Outputs: g_x0 (M,B,5) or NULL (not wanted); dv (M,B,T) = dL/d(each controller's clamped fp32 output); g_w_inp
+ * (M,hidden,3), g_b_inp (M,hidden), g_w_out (M,hidden) in fp64, model m's the bits fcr_closed_loop_vjp gives for model m
+ * alone. ws: device scratch of fcr_closed_loop_bank_vjp_workspace_size bytes (M times the single model's, plus the
+ * loss's partial sums). Conventions at the singular points: fcr_closed_loop_vjp's.
+ *
+ *   fcr_closed_loop_bank_vjp: the general vector-Jacobian product, g_x (M,B,T+1,5) and g_u (M,B,T) incoming.
+ *     T = 0: g_x0 = g_x[:,:,0] and zero parameter gradients.
+ *   fcr_closed_loop_bank_loss_vjp: the gradient of the MPC loss on the record, whose cotangents are formed in registers
+ *     (nothing but the record is read). In fp64, with s_v = ref_scale, s_u = out_scale, (s_p1, s_p2) = p_scale and model
+ *     m's row (alpha, p1_lo, p1_hi, p2_lo, p2_hi, w):
+ *       e_t = (x[t+1,1] - ref[t]) / s_v;  d_t = (u_t - u_{t-1}) / s_u, d_0 = (u_0 - u_prev[b]) / s_u or 0 (u_prev NULL);
+ *       c_t = w (relu(p1_lo - P1) + relu(P1 - p1_hi) + relu(p2_lo - P2) + relu(P2 - p2_hi)), P1 = x[t+1,2] / s_p1,
+ *       P2 = x[t+1,3] / s_p2;  cost[m,b] = (1/T) sum_t (e_t^2 + alpha d_t^2 + c_t);  loss[m] = (1/B) sum_b cost[m,b],
+ *     summed in a fixed order without atomics (the same call twice gives the same bits). relu'(0) = 0; an infinite bound
+ *     switches its side off. terms is the DEVICE table the kernel reads, (M,6) fp64, row m * terms_stride (6, or 0: one
+ *     row for all); terms_host is the same rows in HOST memory, which the call checks before any device call: no NaN,
+ *     lo <= hi, w >= 0. u_prev: (B) shared (u_prev_stride 0) or (M,B) (stride B), or NULL. value_only != 0: only cost
+ *     and loss are computed and every gradient pointer may be NULL. T = 0: zero loss, cost and gradients.
+ * n_models = 0 or B = 0 is a no-op; outputs are zeroed where given and not empty. Stream-ordered; nothing allocates.
+ */
+typedef struct fcr_closed_loop_bank_grad {
+    int32_t n_models, B, T;
+    double ts;
+    int32_t substeps, smooth;
+    const double *ref;
+    int64_t ref_stride;
+    const float *ctrl_w_inp, *ctrl_b_inp, *ctrl_w_out;
+    int32_t ctrl_hidden;
+    double in_scale[2];
+    double ref_scale, out_scale;
+    const double *x, *u;                                 /* the forward's outputs */
+    const double *press;
+    int64_t stride_model, stride_traj;
+    int32_t truncate;
+    double *g_x0, *dv;
+    double *g_w_inp, *g_b_inp, *g_w_out;
+} fcr_closed_loop_bank_grad;
+
+typedef struct fcr_press_loss {
+    const double *terms;                                 /* device, (M,6) fp64 */
+    int64_t terms_stride;
+    const double *terms_host;                            /* host, the same rows: n_models of them, or one (stride 0) */
+    double p_scale[2];
+    const double *u_prev;
+    int64_t u_prev_stride;
+    int32_t value_only;
+    double *cost, *loss;                                 /* (M,B), (M) */
+} fcr_press_loss;
+
+int fcr_closed_loop_bank_vjp_workspace_size(int32_t n_models, int32_t B, int32_t T, int32_t ctrl_hidden, size_t *bytes);
+int fcr_closed_loop_bank_vjp(const fcr_closed_loop_bank_grad *args, const double *g_x, const double *g_u, void *ws,
+                             size_t ws_bytes, void *stream);
+int fcr_closed_loop_bank_loss_vjp(const fcr_closed_loop_bank_grad *args, const fcr_press_loss *loss, void *ws,
+                                  size_t ws_bytes, void *stream);
+
+/*
  * Training-sample windows: the tables of the concatenated per-trajectory
  * SequenceDatasets (Functions.py:92-132, built by Data.get_individual_dataset :479-516 and
  * ConcatDataset, UL/Main.py:270-279), resident in device memory.
