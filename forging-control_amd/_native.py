@@ -41,7 +41,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_forward_many_terms", "fcr_backward_many_terms", "fcr_plant_rk4_vjp", "fcr_closed_loop_vjp_workspace_size",
            "fcr_closed_loop_vjp", "fcr_plant_rk4_vjp_press", "fcr_closed_loop_vjp_press",
            "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum", "fcr_closed_loop_bank_vjp_workspace_size",
-           "fcr_closed_loop_bank_vjp", "fcr_closed_loop_bank_loss_vjp")
+           "fcr_closed_loop_bank_vjp", "fcr_closed_loop_bank_loss_vjp", "fcr_mpc_workspace_size", "fcr_mpc_solve",
+           "fcr_mpc_closed_loop")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -203,6 +204,30 @@ class FcrPressLoss(ctypes.Structure):
     ]
 
 
+class FcrMpc(ctypes.Structure):
+    """fcr_mpc (include/fcr.h): the shooting MPC's horizon, iteration count, integrator, weights and bounds."""
+    _fields_ = [
+        ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("ts", ctypes.c_double),
+        ("substeps", ctypes.c_int32), ("smooth", ctypes.c_int32),
+        ("r_u", ctypes.c_double), ("lam0", ctypes.c_double), ("p_bounds", ctypes.c_double * 4),
+        ("p_weight", ctypes.c_double), ("p_scale", ctypes.c_double), ("u_bounds", ctypes.c_double * 2),
+    ]
+
+
+class FcrMpcLoop(ctypes.Structure):
+    """fcr_mpc_loop (include/fcr.h): the inputs and outputs of the MPC's closed loop."""
+    _fields_ = [
+        ("B", ctypes.c_int32), ("T", ctypes.c_int32), ("preview", ctypes.c_int32),
+        ("x0", ctypes.c_void_p), ("ref", ctypes.c_void_p), ("u_init", ctypes.c_void_p), ("U0", ctypes.c_void_p),
+        ("process_noise", ctypes.c_void_p), ("meas_noise", ctypes.c_void_p),
+        ("plant", ctypes.c_void_p), ("plant_stride", ctypes.c_int64),
+        ("model", ctypes.c_void_p), ("model_stride", ctypes.c_int64),
+        ("x", ctypes.c_void_p), ("u", ctypes.c_void_p), ("cost", ctypes.c_void_p), ("grad_inf", ctypes.c_void_p),
+        ("accepted", ctypes.c_void_p),
+        ("plans", ctypes.c_void_p), ("trace", ctypes.c_void_p), ("trace_u", ctypes.c_void_p),
+    ]
+
+
 class FcrSupervised(ctypes.Structure):
     """fcr_supervised (include/fcr.h): one epoch of the supervised baseline for n_models stacked FNNModels."""
     _fields_ = [
@@ -256,7 +281,8 @@ _SIGNATURES = (
     ("fcr_wide_bwd_cell", _i32, [_i32, _i32, _i32] + [_vp] * 11 + [_sz, _vp]),
 )
 # Pure additions to ABI 8 that an FCR_LIB development build may predate, each under the symbol load() probes for: the press
-# as data, the loss's terms as data, the differentiable press, its gradients with respect to the press parameters
+# as data, the loss's terms as data, the differentiable press, its gradients with respect to the press parameters, training a
+# bank on the press, the MPC baseline
 _ADDITIONS = {
     "fcr_press_nominal": (
         ("fcr_press_nominal", None, [_press]),
@@ -286,6 +312,11 @@ _ADDITIONS = {
         ("fcr_closed_loop_bank_vjp_workspace_size", _i32, [_i32, _i32, _i32, _i32, _P(_sz)]),
         ("fcr_closed_loop_bank_vjp", _i32, [_P(FcrClosedLoopBankGrad), _vp, _vp, _vp, _sz, _vp]),
         ("fcr_closed_loop_bank_loss_vjp", _i32, [_P(FcrClosedLoopBankGrad), _P(FcrPressLoss), _vp, _sz, _vp]),
+    ),
+    "fcr_mpc_solve": (                                       # the MPC baseline on the press
+        ("fcr_mpc_workspace_size", _i32, [_i32, _i32, _P(_sz)]),
+        ("fcr_mpc_solve", _i32, [_P(FcrMpc), _i32, _vp, _vp, _vp, _vp, _vp, _i64] + [_vp] * 7 + [_vp, _sz, _vp]),
+        ("fcr_mpc_closed_loop", _i32, [_P(FcrMpc), _P(FcrMpcLoop), _vp, _sz, _vp]),
     ),
 }
 

@@ -571,6 +571,75 @@ int fcr_closed_loop_bank_loss_vjp(const fcr_closed_loop_bank_grad *args, const f
                                   size_t ws_bytes, void *stream);
 
 /*
+ * The model-predictive baseline on the press (a pure addition to ABI 8): a shooting MPC with the
+ * reference's objective on the RK4 press, one lane per trajectory, all in fp64.
+ *
+ * Problem of one trajectory: state x_0 (5), previous command u_prev, references r_1..r_N and a press row (the
+ * controller's MODEL of the press); unknowns U = (u_0..u_{N-1}); x_{k+1} = one sampling step of fcr_plant_rk4 (ts,
+ * substeps, smooth) under u_k. Residuals: e_k = x_k[1] - r_k, k = 1..N; d_k = sqrt(r_u) (u_k - u_{k-1}), u_{-1} = u_prev,
+ * k = 0..N-1; for k = 1..N the squared hinges sqrt(w) relu((x_k[2] - p1_hi)/s_p), sqrt(w) relu((p1_lo - x_k[2])/s_p) and
+ * the same two for x_k[3] with p2_lo, p2_hi (p_bounds = {p1_lo, p1_hi, p2_lo, p2_hi}; an infinite bound switches its row
+ * off, relu'(0) = 0, w = p_weight = 0 removes all four, s_p = p_scale). cost = sum residual^2. Command box
+ * u_bounds[0] <= u_k <= u_bounds[1] (+-inf = none).
+ *
+ * The solver runs exactly K Levenberg-Marquardt iterations from lambda = lam0. One iteration from (U, lambda, c = cost(U)):
+ * step Jacobians A_k, b_k by the press's adjoint (fcr_plant_rk4_vjp's step under unit cotangents: its conventions at the
+ * singular points); H = J^T J, g = J^T r; active set {i: (U_i <= u_lo and g_i > 0) or (U_i >= u_hi and g_i < 0)}: row and
+ * column i of H zeroed, H_ii = 1, g_i = 0; (H + lambda diag(H)) delta = -g by Cholesky with diag(H) taken before that
+ * substitution; a pivot that is not positive and finite rejects the iteration; U' = clip(U + delta, u_bounds);
+ * c' = cost(U'); accept iff c' < c (false for NaN): U = U', c = c', lambda = max(0.3 lambda, 1e-12); else
+ * lambda = min(10 lambda, 1e12).
+ *
+ *   fcr_mpc_solve: one horizon for B problems. x0 (B,5), ref (B,N), u_prev (B), U0 (B,N) the initial guess or NULL
+ *     (u_prev repeated); the initial guess is projected into u_bounds on load, so U is inside the box even when no
+ *     iteration is accepted, while u_prev in d_0 is taken as given. model: the press rows, trajectory b reads model + b * model_stride (0: one row shared; else a
+ *     multiple of 28), NULL = the reference's press. Outputs U (B,N), cost (B), grad_inf (B) = |g|_inf over the
+ *     non-active entries at the last point linearised, accepted (B) int32, lam (B). trace (B,K,5) with trace_u (B,K,N),
+ *     both or neither (NULL in production): per iteration (c, c', lambda before, accepted 0/1, pivot failure 0/1;
+ *     c' = inf at a pivot failure) and U after the iteration.
+ *   fcr_mpc_closed_loop: for t = 0..T-1 the record m_t = x[:,t] (x_t, plus meas_noise[b,t-1] as fcr_closed_loop_run
+ *     records it) -> r_k = ref[b, min(t+k-1, T-1)] (preview = 1) or ref[b, t] (0) -> a solve from m_t with u_prev = u_{t-1}
+ *     (u_init[b] at t = 0) warm-started from the previous plan shifted by one, its last entry repeated (t = 0: U0 or
+ *     u_init repeated, projected into u_bounds) -> u_t = U[0] -> the TRUE press steps (row plant + b * plant_stride, NULL = the reference's;
+ *     process_noise[b,t] added to every stage as fcr_closed_loop_run does). Outputs x (B,T+1,5), u, cost, grad_inf (B,T),
+ *     accepted (B,T) int32; optional plans (B,T,N), the plan after each step's solve, and trace (B,T,K,5) with trace_u
+ *     (B,T,K,N). T = 0 writes x[:,0] = x0 only.
+ *   ws: device scratch of fcr_mpc_workspace_size(B, N) bytes, the lanes' matrices laid out [element][lane].
+ * Refused before any device call, with a message: N outside 1..32, K outside 1..64, a lower bound above its upper one,
+ * p_weight < 0, r_u < 0, lam0 <= 0, p_scale <= 0, a stride that is negative or no multiple of 28 or comes without its
+ * table, a NULL required pointer, a workspace too small. B = 0 is a no-op. Stream-ordered; nothing allocates.
+ */
+typedef struct fcr_mpc {
+    int32_t N, K;
+    double ts;
+    int32_t substeps, smooth;
+    double r_u, lam0;
+    double p_bounds[4];
+    double p_weight, p_scale;
+    double u_bounds[2];
+} fcr_mpc;
+
+typedef struct fcr_mpc_loop {
+    int32_t B, T, preview;
+    const double *x0, *ref;                              /* (B,5), (B,T) */
+    const double *u_init, *U0;                           /* (B); (B,N) or NULL */
+    const double *process_noise, *meas_noise;            /* (B,T,5) each, or NULL */
+    const double *plant;
+    int64_t plant_stride;
+    const double *model;
+    int64_t model_stride;
+    double *x, *u, *cost, *grad_inf;
+    int32_t *accepted;
+    double *plans, *trace, *trace_u;                     /* optional */
+} fcr_mpc_loop;
+
+int fcr_mpc_workspace_size(int32_t B, int32_t N, size_t *bytes);
+int fcr_mpc_solve(const fcr_mpc *mpc, int32_t B, const double *x0, const double *ref, const double *u_prev, const double *U0,
+                  const double *model, int64_t model_stride, double *U, double *cost, double *grad_inf, int32_t *accepted,
+                  double *lam, double *trace, double *trace_u, void *ws, size_t ws_bytes, void *stream);
+int fcr_mpc_closed_loop(const fcr_mpc *mpc, const fcr_mpc_loop *loop, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Training-sample windows: the tables of the concatenated per-trajectory
  * SequenceDatasets (Functions.py:92-132, built by Data.get_individual_dataset :479-516 and
  * ConcatDataset, UL/Main.py:270-279), resident in device memory.
