@@ -42,7 +42,8 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_closed_loop_vjp", "fcr_plant_rk4_vjp_press", "fcr_closed_loop_vjp_press",
            "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum", "fcr_closed_loop_bank_vjp_workspace_size",
            "fcr_closed_loop_bank_vjp", "fcr_closed_loop_bank_loss_vjp", "fcr_mpc_workspace_size", "fcr_mpc_solve",
-           "fcr_mpc_closed_loop")
+           "fcr_mpc_closed_loop", "fcr_closed_loop_run_bank_press_state", "fcr_closed_loop_bank_vjp_noise",
+           "fcr_closed_loop_bank_loss_vjp_noise")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -204,6 +205,12 @@ class FcrPressLoss(ctypes.Structure):
     ]
 
 
+class FcrBankNoise(ctypes.Structure):
+    """fcr_bank_noise (include/fcr.h): the process noise of a noisy bank run (with its model stride) and the states the
+    forward stored beside the record, as the noisy adjoints read them."""
+    _fields_ = [("process_noise", ctypes.c_void_p), ("process_stride", ctypes.c_int64), ("x_state", ctypes.c_void_p)]
+
+
 class FcrMpc(ctypes.Structure):
     """fcr_mpc (include/fcr.h): the shooting MPC's horizon, iteration count, integrator, weights and bounds."""
     _fields_ = [
@@ -282,7 +289,7 @@ _SIGNATURES = (
 )
 # Pure additions to ABI 8 that an FCR_LIB development build may predate, each under the symbol load() probes for: the press
 # as data, the loss's terms as data, the differentiable press, its gradients with respect to the press parameters, training a
-# bank on the press, the MPC baseline
+# bank on the press, the MPC baseline, training on the press under noise
 _ADDITIONS = {
     "fcr_press_nominal": (
         ("fcr_press_nominal", None, [_press]),
@@ -317,6 +324,12 @@ _ADDITIONS = {
         ("fcr_mpc_workspace_size", _i32, [_i32, _i32, _P(_sz)]),
         ("fcr_mpc_solve", _i32, [_P(FcrMpc), _i32, _vp, _vp, _vp, _vp, _vp, _i64] + [_vp] * 7 + [_vp, _sz, _vp]),
         ("fcr_mpc_closed_loop", _i32, [_P(FcrMpc), _P(FcrMpcLoop), _vp, _sz, _vp]),
+    ),
+    "fcr_closed_loop_bank_vjp_noise": (                      # training on the press under noise
+        ("fcr_closed_loop_run_bank_press_state", _i32, [_P(FcrClosedLoopBank), _vp, _i64, _i64, _press, _vp, _vp]),
+        ("fcr_closed_loop_bank_vjp_noise", _i32, [_P(FcrClosedLoopBankGrad), _P(FcrBankNoise), _vp, _vp, _vp, _sz, _vp]),
+        ("fcr_closed_loop_bank_loss_vjp_noise", _i32,
+         [_P(FcrClosedLoopBankGrad), _P(FcrBankNoise), _P(FcrPressLoss), _vp, _sz, _vp]),
     ),
 }
 

@@ -242,8 +242,9 @@ class ClosedLoop(_LoopConfig):
         derivative is singular are :func:`~.plant.forging_rk4`'s: deformation force differentiated only where ``y > 0``
         and ``y_dot > 0``; valve-flow derivatives 0 at a zero pressure difference, branch by ``z >= 0``; friction slope
         ``FT/0.5`` where ``|y_dot| <= 0.5``, else 0; smooth floor ``0.5 (1 + p / sqrt(p^2 + eps))``. Raises ``ValueError``
-        with ``process_noise``, ``meas_noise`` (the record ``x + v`` does not give the unperturbed state back exactly) or
-        ``feasibility`` (the projection is not differentiable). No gradient reaches ``ref``. Gradients through the press
+        with ``process_noise``, ``meas_noise`` (the record ``x + v`` does not give the unperturbed state back exactly:
+        :meth:`run_differentiable` stores it and is the call under noise) or ``feasibility`` (the projection is not
+        differentiable). No gradient reaches ``ref``. Gradients through the press
         grow with T: back-propagation through hundreds of steps is the caller's risk.
 
         Gradients reach the press too: a ``plant_params`` tensor, ``(28,)`` or ``(B,28)``, that requires
@@ -260,7 +261,8 @@ class ClosedLoop(_LoopConfig):
             for name, given in (("process_noise", process_noise), ("meas_noise", meas_noise), ("feasibility", feasibility)):
                 if given is not None:
                     raise ValueError(f"ClosedLoop.run(differentiable=True) does not take {name}: the adjoint covers the "
-                                     "noise-free loop without recovery (DESIGN.md §7.13)")
+                                     "noise-free loop without recovery (DESIGN.md §7.13); under noise: run_differentiable "
+                                     "(§7.18)")
             if torch.is_grad_enabled():
                 return _ClosedLoopGrad.apply(self, x0, ref, plant_params, *_controller_params(self.controller))
         if plant_params is not None or (feasibility is not None and feasibility.model_params is not None):
@@ -281,6 +283,26 @@ class ClosedLoop(_LoopConfig):
         if feasibility is None:
             return out["x"], out["u"]
         return out["x"], out["u"], {"u_nn": out["u_nn"], "flag": out["flag"]}
+
+    def run_differentiable(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
+                           meas_noise: torch.Tensor | None = None, plant_params=None, truncate: int = 0, p_bounds=None):
+        """:meth:`ClosedLoopBank.run_differentiable` for this loop as a bank of one: ``x0 (B,5)``,
+        ``ref (B,T)``, each noise ``(B,T,5)`` or ``None``, ``plant_params`` as :meth:`run` takes it (a constant here).
+        Returns the bank's dict with ``x (B,T+1,5)`` and ``u (B,T)`` attached to the controller's parameters and to
+        ``x0``, and the detached ``x_state (B,T+1,5)``, each without the model dimension; every other entry is the bank
+        of one's (leading dimension 1)."""
+        if plant_params is None:
+            plant_params = self.plant_params
+        if x0.dim() != 2 or ref.dim() != 2:
+            raise ValueError(f"x0 must be (B,5) and ref (B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
+        if plant_params is not None and _press_shape(plant_params) not in ((28,), (x0.shape[0], 28)):
+            raise ValueError(f"plant_params must be a PressParams, (28,) or (B,28) with B = {x0.shape[0]}, got shape "
+                             f"{_press_shape(plant_params)}")
+        w_inp, b_inp, w_out = _controller_params(self.controller)
+        out = ClosedLoopBank.of_loop(self).run_differentiable(
+            x0, ref, process_noise, meas_noise, plant_params, truncate, p_bounds,
+            _weights=(w_inp[None], b_inp[None], w_out.reshape(1, -1)))
+        return {**out, "x": out["x"][0], "u": out["u"][0], "x_state": out["x_state"][0]}
 
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
              process_noise: torch.Tensor | None = None, meas_noise: torch.Tensor | None = None,
@@ -486,12 +508,44 @@ class ClosedLoopBank(_LoopConfig):
             for name, v in given.items():
                 if v is not None:
                     raise ValueError(f"ClosedLoopBank.run(differentiable=True) does not take {name}: the adjoint covers "
-                                     "the stored noise-free loop without recovery (DESIGN.md §7.13, §7.16)")
+                                     "the stored noise-free loop without recovery (DESIGN.md §7.13, §7.16); under noise: "
+                                     "run_differentiable (§7.18)")
             if torch.is_grad_enabled():
                 holder = {}
                 x, u = _ClosedLoopBankGrad.apply(self, holder, p_bounds, x0, ref, plant_params, self.bank.w_inp,
                                                  self.bank.b_inp, self.bank.w_out)
                 return {**holder["out"], "x": x, "u": u}
+        return self._launch(x0, ref, process_noise, meas_noise, feasibility, store, p_bounds, plant_params)
+
+    def run_differentiable(self, x0: torch.Tensor, ref: torch.Tensor, process_noise: torch.Tensor | None = None,
+                           meas_noise: torch.Tensor | None = None, plant_params=None, truncate: int = 0, p_bounds=None,
+                           _weights=None):
+        """:meth:`run` under pre-drawn noise, attached to the graph: :meth:`run`'s dict with ``x`` and
+        ``u`` attached to the bank's stacked parameters and to ``x0``, plus ``x_state (M,B,T+1,5)``, the unperturbed
+        states (detached; without ``meas_noise`` it is the record). ``process_noise`` / ``meas_noise``: ``(B,T,5)``
+        shared or ``(M,B,T,5)``, constants — no gradient reaches them (:func:`harness_noise`, :func:`device_noise`).
+        ``x``, ``u`` and the metrics are ``run(process_noise=, meas_noise=)``'s bit for bit; without noise the call is
+        ``run(differentiable=True)``. Under ``torch.no_grad()`` everything comes back detached.
+
+        The backward is one reverse launch (``fcr_closed_loop_bank_vjp_noise``): the incoming gradients are those on the
+        RECORD ``x`` (``= x_state + v``, so they are the state's too); the controller's chain and masks are taken from the
+        record it read; the plant is linearised at the state, with the step's noise at every RK4 stage. ``truncate = K``:
+        truncated back-propagation, as :func:`bank_vjp`'s. Conventions at the singular points: :meth:`ClosedLoop.run`'s.
+        Not covered: feasibility recovery, gradients with respect to the noise, ``ref`` or the press."""
+        if int(truncate) != truncate or int(truncate) < 0:
+            raise ValueError(f"run_differentiable: truncate = {truncate!r} must be an integer >= 0 (0 = none)")
+        weights = (self.bank.w_inp, self.bank.b_inp, self.bank.w_out) if _weights is None else _weights
+        if not torch.is_grad_enabled():
+            return self._launch(x0, ref, process_noise, meas_noise, None, True, p_bounds, plant_params,
+                                with_state=True)
+        holder = {}
+        x, u = _NoisyBankGrad.apply(self, holder, p_bounds, int(truncate), x0, ref, process_noise, meas_noise, plant_params,
+                                    *weights)
+        return {**holder["out"], "x": x, "u": u}
+
+    def _launch(self, x0, ref, process_noise, meas_noise, feasibility, store, p_bounds, plant_params, with_state=False):
+        """The forward launch of :meth:`run`. ``with_state``: the returned dict gains ``x_state`` — under ``meas_noise``
+        stored by the launch itself (``fcr_closed_loop_run_bank_press_state``), otherwise the record."""
         M = self.bank.w_inp.shape[0]
         dev, B, T, stacked, out, prefix, keep = self._prepare(M, (self.bank.w_inp, self.bank.b_inp, self.bank.w_out), x0, ref,
                                                               process_noise, meas_noise, feasibility, store)
@@ -512,7 +566,13 @@ class ClosedLoopBank(_LoopConfig):
             p(out["traj_counts"]), p(out["x_final"]), p(summary))
         model = None if feasibility is None else feasibility.model_params
         name, extra = "fcr_closed_loop_run_bank", ()
-        if plant_params is not None or model is not None:
+        if with_state and meas_noise is not None:
+            table = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+            out["x_state"] = torch.empty(M, B, T + 1, 5, dtype=torch.float64, device=dev)
+            name = "fcr_closed_loop_run_bank_press_state"
+            extra = (None if table is None else p(table), B * 28 if table is not None and table.dim() == 3 else 0,
+                     28 if table is not None and table.dim() >= 2 else 0, None, p(out["x_state"]))
+        elif plant_params is not None or model is not None:
             table = as_press_table(PressParams() if plant_params is None else plant_params, dev, "plant_params")
             m_struct = None if model is None else model.struct()
             name = "fcr_closed_loop_run_bank_press"
@@ -522,6 +582,8 @@ class ClosedLoopBank(_LoopConfig):
         if M == 0 or B == 0:
             summary.zero_()
         out["metrics"] = {k: summary[:, i] for i, k in enumerate(METRIC_KEYS)}
+        if with_state and "x_state" not in out:
+            out["x_state"] = out["x"]
         return out
 
     def loop(self, x0: torch.Tensor, ref: torch.Tensor, simulator, model_scalers: dict,
@@ -585,6 +647,64 @@ class _ClosedLoopBankGrad(torch.autograd.Function):
         return (None, None, None, g_x0, None, None, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_), like(g["g_w_out"], wo_))
 
 
+class _NoisyBankGrad(torch.autograd.Function):
+    """:meth:`ClosedLoopBank.run_differentiable` attached to the graph: the forward is the bank's launch under the given
+    noise (storing the states beside the record under measurement noise), the backward :func:`bank_vjp` on the stored run
+    with that noise. ``holder['out']`` receives the run's whole dict, ``x_state`` included."""
+
+    @staticmethod
+    def forward(ctx, loop, holder, p_bounds, truncate, x0, ref, process_noise, meas_noise, plant_params, w_inp, b_inp, w_out):
+        if torch.is_tensor(plant_params):
+            plant_params = plant_params.detach()
+        out = loop._launch(x0, ref, process_noise, meas_noise, None, True, p_bounds, plant_params, with_state=True)
+        holder["out"] = dict(out)
+        x, u = out["x"], out["u"]
+        dev = x.device
+        ctx.loop, ctx.truncate = loop, truncate
+        ctx.tab = None if plant_params is None else as_press_table(plant_params, dev, "plant_params")
+        ctx.like = tuple((t.shape, t.device, t.dtype) for t in (x0, w_inp, b_inp, w_out))
+        ctx.noisy = (process_noise is not None, meas_noise is not None)
+        ctx.save_for_backward(x, u, ref.to(torch.float64).contiguous(),
+                              *(p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in (w_inp, b_inp, w_out)),
+                              process_noise.detach() if ctx.noisy[0] else None, out["x_state"] if ctx.noisy[1] else None)
+        return x, u
+
+    @staticmethod
+    def backward(ctx, g_x, g_u):
+        x, u, ref, w_inp, b_inp, w_out, process_noise, x_state = ctx.saved_tensors
+        g = bank_vjp(ctx.loop, x, u, ref, g_x, g_u, (w_inp, b_inp, w_out), ctx.tab, truncate=ctx.truncate,
+                     want_x0=ctx.needs_input_grad[4], process_noise=process_noise, x_state=x_state)
+        like = lambda t, to: t.reshape(to[0]).to(device=to[1], dtype=to[2])
+        x0_, wi_, bi_, wo_ = ctx.like
+        g_x0 = None
+        if ctx.needs_input_grad[4]:
+            g_x0 = like(g["g_x0"] if len(x0_[0]) == 3 else g["g_x0"].sum(0), x0_)   # a shared x0: the sum over the models
+        return (None, None, None, None, g_x0, None, None, None, None, like(g["g_w_inp"], wi_), like(g["g_b_inp"], bi_),
+                like(g["g_w_out"], wo_))
+
+
+def device_noise(B: int, T: int, process_std, meas_std, device, generator: torch.Generator | None = None, M: int | None = None):
+    """Noise for training, drawn with torch on ``device``: ``(w, v)``, each fp64 ``(B,T,5)`` (``M`` given: ``(M,B,T,5)``, a
+    draw per model) or ``None`` where its standard deviations (a number or five, per state) are all zero or ``None``.
+    ``w = process_std * N(0,1)`` in the units of x_dot, ``v = meas_std * N(0,1)`` in the units of the state, as
+    :meth:`ClosedLoopBank.run` takes them. It does NOT follow the reference's draw order (one numpy stream, 14 values per
+    step, trajectory by trajectory): two runs from equal ``generator`` states agree with each other and with nothing else.
+    :func:`harness_noise` is the one that reproduces the harness's draws."""
+    shape = ((int(B), int(T), 5) if M is None else (int(M), int(B), int(T), 5))
+
+    def draw(std, name):
+        if std is None:
+            return None
+        s = torch.as_tensor(std, dtype=torch.float64).reshape(-1)
+        if s.numel() not in (1, 5) or bool((s < 0).any()) or not bool(torch.isfinite(s).all()):
+            raise ValueError(f"device_noise: {name} must be one or five finite standard deviations >= 0, got {std!r}")
+        if not bool((s > 0).any()):
+            return None
+        return torch.randn(shape, dtype=torch.float64, device=device, generator=generator) * s.to(device)
+
+    return draw(process_std, "process_std"), draw(meas_std, "meas_std")
+
+
 def _bank_adjoint(who, loop, x, u, ref, weights, plant_params, truncate, want_x0, want_grads=True):
     """What :func:`bank_vjp` and :func:`bank_loss_vjp` share: the checks, the conversions, the outputs, the workspace and
     the ``fcr_closed_loop_bank_grad`` of the call. Returns ``(args, out, ws, keep)``."""
@@ -631,20 +751,52 @@ def _bank_adjoint(who, loop, x, u, ref, weights, plant_params, truncate, want_x0
     return args, out, ws, (x, u, ref, w_inp, b_inp, w_out, tab)
 
 
+def _bank_noise(who, process_noise, x_state, x, keep):
+    """The ``fcr_bank_noise`` of a noisy run's adjoint, or ``None`` when the run had no noise:
+    ``process_noise`` ``(B,T,5)`` shared or ``(M,B,T,5)``, ``x_state`` the forward's states, shaped as ``x``."""
+    if process_noise is None and x_state is None:
+        return None
+    dev, (M, B, T) = x.device, x.shape[:2] + (x.shape[2] - 1,)
+    f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()
+    stride = 0
+    if process_noise is not None:
+        stride = B * T * 5 if _per_model("process_noise", process_noise, M, (B, T, 5)) else 0
+        process_noise = f64(process_noise)
+    if x_state is not None:
+        if tuple(x_state.shape) != tuple(x.shape):
+            raise ValueError(f"{who}: x_state must have x's shape {tuple(x.shape)}, got {tuple(x_state.shape)}")
+        x_state = f64(x_state)
+    keep.extend((process_noise, x_state))
+    p = lambda t: None if t is None else t.data_ptr()
+    return _native.FcrBankNoise(p(process_noise), stride, p(x_state))
+
+
 def bank_vjp(loop: "ClosedLoopBank", x, u, ref, g_x, g_u, weights=None, plant_params=None, truncate: int = 0,
-             want_x0: bool = True) -> dict:
+             want_x0: bool = True, process_noise=None, x_state=None) -> dict:
     """:func:`loop_vjp` for the M models of a :class:`ClosedLoopBank` in one reverse launch (``fcr_closed_loop_bank_vjp``):
     from the stored ``x (M,B,T+1,5)``, ``u (M,B,T)``, the run's ``ref`` (``(B,T)`` shared or ``(M,B,T)``) and the incoming
     ``g_x``, ``g_u`` of those shapes, a dict of fp64 tensors ``g_x0 (M,B,5)`` (``None`` with ``want_x0=False``),
     ``dv (M,B,T)``, ``g_w_inp (M,H,3)``, ``g_b_inp (M,H)``, ``g_w_out (M,H)`` — model m's are :func:`loop_vjp`'s for that
     model alone. ``weights``: the bank's three stacked parameters as the run read them (default: the bank's now);
     ``plant_params``: the run's, in any of its four forms. ``truncate = K > 0``: the states at ``t = K, 2K, ... < T``
-    count as constants for the step that starts from them (``x = x.detach()`` there)."""
+    count as constants for the step that starts from them (``x = x.detach()`` there).
+
+    ``process_noise`` / ``x_state``: the run was made under noise (:meth:`ClosedLoopBank.run_differentiable`; DESIGN.md
+    §7.18) — its process noise, ``(B,T,5)`` shared or ``(M,B,T,5)``, and the unperturbed states that run returned
+    (``None``: no measurement noise, the record is the state). ``g_x`` is then the gradient on the record; the plant is
+    linearised at the state with the step's noise (``fcr_closed_loop_bank_vjp_noise``)."""
     args, out, ws, keep = _bank_adjoint("bank_vjp", loop, x, u, ref, weights, plant_params, truncate, want_x0)
     dev, (M, B, T) = keep[0].device, keep[1].shape
     if tuple(g_x.shape) != (M, B, T + 1, 5) or tuple(g_u.shape) != (M, B, T):
         raise ValueError(f"bank_vjp: g_x must be (M,B,T+1,5) and g_u (M,B,T); got {tuple(g_x.shape)}, {tuple(g_u.shape)}")
     gx, gu = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (g_x, g_u))
+    held = []
+    noise = _bank_noise("bank_vjp", process_noise, x_state, keep[0], held)
+    if noise is not None:
+        _native.check(_native.load().fcr_closed_loop_bank_vjp_noise(
+            ctypes.byref(args), ctypes.byref(noise), ctypes.c_void_p(gx.data_ptr()), ctypes.c_void_p(gu.data_ptr()),
+            ctypes.c_void_p(ws.data_ptr()), ws.numel(), _native.stream(dev)), "fcr_closed_loop_bank_vjp_noise")
+        return out
     _native.check(_native.load().fcr_closed_loop_bank_vjp(
         ctypes.byref(args), ctypes.c_void_p(gx.data_ptr()), ctypes.c_void_p(gu.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
         ws.numel(), _native.stream(dev)), "fcr_closed_loop_bank_vjp")
@@ -652,12 +804,14 @@ def bank_vjp(loop: "ClosedLoopBank", x, u, ref, g_x, g_u, weights=None, plant_pa
 
 
 def bank_loss_vjp(loop: "ClosedLoopBank", x, u, ref, terms_rows, p_scale, u_prev=None, weights=None, plant_params=None,
-                  truncate: int = 0, want_x0: bool = True, value_only: bool = False) -> dict:
+                  truncate: int = 0, want_x0: bool = True, value_only: bool = False, process_noise=None,
+                  x_state=None) -> dict:
     """The MPC loss on the stored run of a bank and its gradient in one reverse launch
     (``fcr_closed_loop_bank_loss_vjp``; the loss: :class:`~.press_loss.PressLoss`). ``terms_rows``: one row
     ``(alpha, p1_lo, p1_hi, p2_lo, p2_hi, weight)`` for all models or one per model; ``p_scale``: the two pressure
     scales; ``u_prev``: ``(B,)`` shared or ``(M,B)``, or ``None``. Returns :func:`bank_vjp`'s dict and ``cost (M,B)``,
-    ``loss (M,)``; ``value_only=True``: those two alone, nothing is differentiated."""
+    ``loss (M,)``; ``value_only=True``: those two alone, nothing is differentiated. ``process_noise`` / ``x_state``: the
+    run was made under noise, as for :func:`bank_vjp` (``fcr_closed_loop_bank_loss_vjp_noise``); the loss is the record's."""
     args, out, ws, keep = _bank_adjoint("bank_loss_vjp", loop, x, u, ref, weights, plant_params, truncate, want_x0,
                                         want_grads=not value_only)
     dev, (M, B, T) = keep[0].device, keep[1].shape
@@ -676,6 +830,13 @@ def bank_loss_vjp(loop: "ClosedLoopBank", x, u, ref, terms_rows, p_scale, u_prev
         (ctypes.c_double * 2)(float(p_scale[0]), float(p_scale[1])), None if u_prev is None else u_prev.data_ptr(),
         B if u_prev is not None and u_prev.dim() == 2 else 0, int(bool(value_only)), out["cost"].data_ptr(),
         out["loss"].data_ptr())
+    held = []
+    noise = _bank_noise("bank_loss_vjp", process_noise, x_state, keep[0], held)
+    if noise is not None:
+        _native.check(_native.load().fcr_closed_loop_bank_loss_vjp_noise(
+            ctypes.byref(args), ctypes.byref(noise), ctypes.byref(loss), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+            _native.stream(dev)), "fcr_closed_loop_bank_loss_vjp_noise")
+        return out
     _native.check(_native.load().fcr_closed_loop_bank_loss_vjp(
         ctypes.byref(args), ctypes.byref(loss), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _native.stream(dev)),
         "fcr_closed_loop_bank_loss_vjp")

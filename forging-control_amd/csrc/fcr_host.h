@@ -6,6 +6,9 @@
 //   fcr_wide.hip     the H > 52 rollout, the H > 52 surrogate step and the fcr_wide_bwd_cell test hook
 //   fcr_rows.hip     plant, closed loop and bank, feasibility projection, window gather, the supervised baseline's epoch
 //   fcr_grad.hip     the press's adjoint: vector-Jacobian products of the plant rollout and the closed loop
+//   fcr_train.hip    the bank's adjoint and the fused loss on the press; fcr_mpc.hip the MPC baseline
+//   fcr_press_noise.hip  the kernels of training under noise; launched from fcr_rows.hip and fcr_train.hip through
+//                    fcr_press_noise_host.h
 // What one file needs of another goes through the functions below. The argument checks fcr_rows.hip and fcr_grad.hip
 // share, and their choice of a kernel instantiation from run-time flags, are in the host-only fcr_press_host.h: it
 // includes fcr_plant.h, so only those two files include it.

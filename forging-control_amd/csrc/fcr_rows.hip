@@ -13,6 +13,7 @@
 #include "fcr_host.h"
 #include "fcr_plant.h"
 #include "fcr_press_host.h"
+#include "fcr_press_noise_host.h"
 #include "fcr_supervised.h"
 #include "fcr_window.h"
 
@@ -101,8 +102,12 @@ Loop loop_of(const C *c) {
 
 // fcr_closed_loop_run_bank (table = null: the reference's press, the kernels without parameters) and
 // fcr_closed_loop_run_bank_press (table's strides and model: checked by the caller)
+// and fcr_closed_loop_run_bank_press_state (state: the storing run that also writes the unperturbed states to x_state,
+// fcr_press_noise.hip's kernels; table = null there too is the reference's press)
 int run_bank(const char *who, const fcr_closed_loop_bank *c, const closed_loop::PressTable *table,
-             const plant::UniformParams *model, void *stream) {
+             const plant::UniformParams *model, void *stream, bool state = false, double *x_state = nullptr) {
+    if (state && c->feasibility)
+        return fail(FCR_EUNSUPPORTED, "%s: x_state is stored by the loop without feasibility recovery", who);
     if (c->n_models < 0) return fail(FCR_EINVAL, "%s: n_models=%d must be >= 0", who, c->n_models);
     if (!(c->p1_lo < c->p1_hi) || !(c->p2_lo < c->p2_hi))
         return fail(FCR_EINVAL, "%s: pressure bounds p1 [%g, %g], p2 [%g, %g] need lo < hi", who, c->p1_lo, c->p1_hi,
@@ -132,13 +137,20 @@ int run_bank(const char *who, const fcr_closed_loop_bank *c, const closed_loop::
     if ((((uintptr_t)c->feas_flag) | ((uintptr_t)c->traj_counts) | ((uintptr_t)c->ctrl_w_inp) | ((uintptr_t)c->ctrl_b_inp) |
          ((uintptr_t)c->ctrl_w_out)) & 3)
         return fail(FCR_EINVAL, "%s: int32 and fp32 buffers must be 4-byte aligned", who);
+    if (state && (!x_state || !c->x)) return fail(FCR_EINVAL, "%s: x_state is stored beside x: both are required", who);
+    if (((uintptr_t)x_state) & 7) return fail(FCR_EINVAL, "%s: x_state must be 8-byte aligned (fp64)", who);
     const closed_loop::BankStrides st{c->x0_stride, c->ref_stride, c->process_noise_stride, c->meas_noise_stride};
     const closed_loop::StatsArgs sa{c->p1_lo, c->p1_hi, c->p2_lo, c->p2_hi, c->traj_stats, c->traj_counts, c->x_final};
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(c->n_models * bpm)), block(closed_loop::kClBlock);
     const bool store = c->x != nullptr;
     const char *what;
-    if (table && l.recover) {
+    if (state) {
+        if (const int rc = press_noise::launch_bank_state(l.a, st, sa, c->process_noise, c->meas_noise, table, l.smooth,
+                                                          x_state, grid, s))
+            return rc;
+        what = "closed_loop_bank_state_kernel";
+    } else if (table && l.recover) {
         const auto k = select([](auto sm, auto noise, auto store) {
             return &feasibility::closed_loop_bank_recover_press_kernel<sm(), noise(), store()>; }, l.smooth, l.noise, store);
         hipLaunchKernelGGL(k, grid, block, 0, s, l.a, fa, st, sa, c->process_noise, c->meas_noise, c->u_nn, c->feas_flag,
@@ -266,6 +278,20 @@ int fcr_closed_loop_run_bank_press(const fcr_closed_loop_bank *c, const double *
     if (const int rc = press_model(who, model, &mp)) return rc;
     const closed_loop::PressTable table{press, (long long)stride_model, (long long)stride_traj};
     return run_bank(who, c, &table, &mp, stream);
+}
+
+int fcr_closed_loop_run_bank_press_state(const fcr_closed_loop_bank *c, const double *press, int64_t stride_model,
+                                         int64_t stride_traj, const fcr_press *model, double *x_state, void *stream) {
+    const char *who = "fcr_closed_loop_run_bank_press_state";
+    if (const int rc = check_loop(who, c, closed_loop::kClMaxHidden, false)) return rc;
+    if (const int rc = check_table_strides(who, stride_model, stride_traj, c->B)) return rc;
+    if (const int rc = check_table_pointer(who, press, false, stride_traj)) return rc;
+    if (!press && stride_model)
+        return fail(FCR_EINVAL, "%s: stride_model=%lld without a parameter table", who, (long long)stride_model);
+    plant::UniformParams mp;
+    if (const int rc = press_model(who, model, &mp)) return rc;
+    const closed_loop::PressTable table{press, (long long)stride_model, (long long)stride_traj};
+    return run_bank(who, c, press ? &table : nullptr, &mp, stream, true, x_state);
 }
 
 int fcr_feasibility_project(const fcr_feasibility *f, int32_t B, const double *x, const double *u_nn, double *u,

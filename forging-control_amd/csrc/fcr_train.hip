@@ -1,6 +1,8 @@
 // fcr_train.hip — C ABI of training a bank of controllers on the press (fcr_press_train.h): the
 // adjoint of the closed loop for M models under incoming gradients (fcr_closed_loop_bank_vjp) or under the MPC loss
-// evaluated on the record (fcr_closed_loop_bank_loss_vjp), and their workspace query. Validation before any device call,
+// evaluated on the record (fcr_closed_loop_bank_loss_vjp), their workspace query, and both on a run made under pre-drawn
+// noise (fcr_closed_loop_bank_vjp_noise, fcr_closed_loop_bank_loss_vjp_noise; §7.18: the same function with one more
+// argument, the reverse launch being fcr_press_noise.hip's). Validation before any device call,
 // by the checks the press rows share (fcr_press_host.h); stream-ordered launches; no allocation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +21,7 @@
 #include "fcr_press_grad.h"
 #pragma pop_macro("__global__")
 
+#include "fcr_press_noise_host.h"
 #include "fcr_press_train.h"
 
 using namespace fcr;
@@ -75,10 +78,27 @@ int check_loss(const char *who, const fcr_press_loss *l, int M, int B) {
     return FCR_OK;
 }
 
-// both entry points under their own names: l = NULL is the general product (g_x, g_u), else the fused loss
+// the noisy run's own arguments (fcr_bank_noise): where the adjoint reads the process noise and the forward's states
+int check_noise(const char *who, const fcr_bank_noise *n, int B, int T) {
+    if (!n) return fail(FCR_EINVAL, "%s: noise is NULL", who);
+    if (n->process_stride < 0 || (n->process_stride && n->process_stride < (long long)B * T * 5))
+        return fail(FCR_EINVAL, "%s: process_stride=%lld must be 0 (shared) or >= B * T * 5 = %lld", who,
+                    (long long)n->process_stride, (long long)B * T * 5);
+    if (!n->process_noise && n->process_stride)
+        return fail(FCR_EINVAL, "%s: process_stride=%lld without process_noise", who, (long long)n->process_stride);
+    if ((((uintptr_t)n->process_noise) | ((uintptr_t)n->x_state)) & 7)
+        return fail(FCR_EINVAL, "%s: process_noise and x_state must be 8-byte aligned (fp64)", who);
+    return FCR_OK;
+}
+
+// the entry points under their own names: l = NULL is the general product (g_x, g_u), else the fused loss; noisy: the
+// adjoint of the run under pre-drawn noise (nz; fcr_press_noise.hip's kernels), everything else as without
 int bank_vjp(const char *who, const fcr_closed_loop_bank_grad *c, const double *g_x, const double *g_u,
-             const fcr_press_loss *l, bool fused, void *ws, size_t ws_bytes, void *stream) {
+             const fcr_press_loss *l, bool fused, void *ws, size_t ws_bytes, void *stream,
+             const fcr_bank_noise *nz = nullptr, bool noisy = false) {
     if (const int rc = check_loop(who, c, press_grad::kMaxHidden, true)) return rc;
+    if (noisy)
+        if (const int rc = check_noise(who, nz, c->B, c->T)) return rc;
     if (const int rc = check_models(who, c->n_models, c->B, c->T)) return rc;
     if (const int rc = check_table_strides(who, c->stride_model, c->stride_traj, c->B)) return rc;
     if (const int rc = check_table_pointer(who, c->press, false, c->stride_traj)) return rc;
@@ -129,6 +149,10 @@ int bank_vjp(const char *who, const fcr_closed_loop_bank_grad *c, const double *
         if (value_only) {
             hipLaunchKernelGGL(press_train::press_loss_value_kernel, grid, block, 0, s, a, seed);
             if (const int rc = launch_check("press_loss_value_kernel")) return rc;
+        } else if (noisy) {
+            const press_noise::NoiseGrad n{nz->process_noise, (long long)nz->process_stride, nz->x_state};
+            if (const int rc = press_noise::launch_bank_vjp(a, nullptr, &seed, n, c->smooth, kept, c->press != nullptr, grid, s))
+                return rc;
         } else {   // T = 0 launches too: zero cost and g_x0
             const auto k = select([](auto sm, auto kp, auto table) {
                 return &press_train::closed_loop_bank_vjp_kernel<sm(), kp(), Press<table()>, press_train::LossSeed>; },
@@ -141,11 +165,17 @@ int bank_vjp(const char *who, const fcr_closed_loop_bank_grad *c, const double *
         if (const int rc = launch_check("cost_sum_kernel")) return rc;
     } else if (B > 0) {   // T = 0 launches too: g_x0 = g_x[:, :, 0]
         const press_train::TensorSeed seed{g_x, g_u};
-        const auto k = select([](auto sm, auto kp, auto table) {
-            return &press_train::closed_loop_bank_vjp_kernel<sm(), kp(), Press<table()>, press_train::TensorSeed>; },
-            c->smooth, kept, c->press != nullptr);
-        hipLaunchKernelGGL(k, grid, block, 0, s, a, seed);
-        if (const int rc = launch_check("closed_loop_bank_vjp_kernel<TensorSeed>")) return rc;
+        if (noisy) {
+            const press_noise::NoiseGrad n{nz->process_noise, (long long)nz->process_stride, nz->x_state};
+            if (const int rc = press_noise::launch_bank_vjp(a, &seed, nullptr, n, c->smooth, kept, c->press != nullptr, grid, s))
+                return rc;
+        } else {
+            const auto k = select([](auto sm, auto kp, auto table) {
+                return &press_train::closed_loop_bank_vjp_kernel<sm(), kp(), Press<table()>, press_train::TensorSeed>; },
+                c->smooth, kept, c->press != nullptr);
+            hipLaunchKernelGGL(k, grid, block, 0, s, a, seed);
+            if (const int rc = launch_check("closed_loop_bank_vjp_kernel<TensorSeed>")) return rc;
+        }
     }
     if (fused && l->loss) {   // B = 0: zeros
         hipLaunchKernelGGL(press_train::loss_reduce_kernel, dim3((M + press_grad::kSumLanes - 1) / press_grad::kSumLanes),
@@ -189,6 +219,17 @@ int fcr_closed_loop_bank_vjp(const fcr_closed_loop_bank_grad *args, const double
 int fcr_closed_loop_bank_loss_vjp(const fcr_closed_loop_bank_grad *args, const fcr_press_loss *loss, void *ws,
                                   size_t ws_bytes, void *stream) {
     return bank_vjp("fcr_closed_loop_bank_loss_vjp", args, nullptr, nullptr, loss, true, ws, ws_bytes, stream);
+}
+
+int fcr_closed_loop_bank_vjp_noise(const fcr_closed_loop_bank_grad *args, const fcr_bank_noise *noise, const double *g_x,
+                                   const double *g_u, void *ws, size_t ws_bytes, void *stream) {
+    return bank_vjp("fcr_closed_loop_bank_vjp_noise", args, g_x, g_u, nullptr, false, ws, ws_bytes, stream, noise, true);
+}
+
+int fcr_closed_loop_bank_loss_vjp_noise(const fcr_closed_loop_bank_grad *args, const fcr_bank_noise *noise,
+                                        const fcr_press_loss *loss, void *ws, size_t ws_bytes, void *stream) {
+    return bank_vjp("fcr_closed_loop_bank_loss_vjp_noise", args, nullptr, nullptr, loss, true, ws, ws_bytes, stream, noise,
+                    true);
 }
 
 }  // extern "C"

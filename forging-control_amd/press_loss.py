@@ -38,7 +38,12 @@ class PressLoss:
     and to ``x0`` (a shared ``(B,5)`` receives the sum over the models); ``plant_params`` in every form and ``u_prev``
     (``(B,)`` or ``(M,B)``) are constants. The gradients are computed in the forward (each model's loss is a scalar, so
     the backward only multiplies model m's by ``g_loss[m]``): ``loss.sum().backward()`` trains every model on its own
-    loss. Under ``torch.no_grad()`` only the forward launch and the loss's value kernel run."""
+    loss. Under ``torch.no_grad()`` only the forward launch and the loss's value kernel run.
+
+    ``forward(..., process_noise=None, meas_noise=None)``: the loop runs under that pre-drawn noise, ``(B,T,5)`` shared
+    by the models or ``(M,B,T,5)`` (:func:`~.closed_loop.harness_noise`, :func:`~.closed_loop.device_noise`):
+    still one forward launch and one fused reverse launch. The loss is evaluated on the record ``x`` (measurement noise
+    included), as the run's metrics are; the noise is a constant. ``features`` then also holds ``x_state``."""
 
     def __init__(self, loop, p_scale, terms=None, alpha: float = 0.1, truncate: int = 0):
         if not isinstance(loop, (ClosedLoop, ClosedLoopBank)):
@@ -72,14 +77,15 @@ class PressLoss:
         w_inp, b_inp, w_out = _controller_params(self.loop.controller)
         return ClosedLoopBank.of_loop(self.loop), (w_inp[None], b_inp[None], w_out.reshape(1, -1))
 
-    def forward(self, x0, ref, plant_params=None, u_prev=None):
+    def forward(self, x0, ref, plant_params=None, u_prev=None, process_noise=None, meas_noise=None):
         if plant_params is None and isinstance(self.loop, ClosedLoop):
             plant_params = self.loop.plant_params
         if isinstance(self.loop, ClosedLoop) and (x0.dim() != 2 or ref.dim() != 2):
             raise ValueError(f"x0 must be (B,5) and ref (B,T); got {tuple(x0.shape)}, {tuple(ref.shape)}")
         bank_loop, weights = self._bank()
         features = {}
-        loss = _PressLossFn.apply(self, bank_loop, features, x0, ref, plant_params, u_prev, *weights)
+        loss = _PressLossFn.apply(self, bank_loop, features, x0, ref, plant_params, u_prev, *weights, process_noise,
+                                  meas_noise)
         return loss, features
 
     __call__ = forward
@@ -90,16 +96,24 @@ class _PressLossFn(torch.autograd.Function):
     kernel alone). Backward: model m's gradients times ``g_loss[m]``."""
 
     @staticmethod
-    def forward(ctx, pl, bank_loop, features, x0, ref, plant_params, u_prev, w_inp, b_inp, w_out):
+    def forward(ctx, pl, bank_loop, features, x0, ref, plant_params, u_prev, w_inp, b_inp, w_out, process_noise=None,
+                meas_noise=None):
         if torch.is_tensor(plant_params):
             plant_params = plant_params.detach()
-        r = bank_loop.run(x0.detach(), ref, plant_params=plant_params)
+        noisy = process_noise is not None or meas_noise is not None
+        if noisy:   # the same launch under noise; under measurement noise it stores the states beside the record
+            r = bank_loop._launch(x0.detach(), ref, process_noise, meas_noise, None, True, None, plant_params, with_state=True)
+        else:
+            r = bank_loop.run(x0.detach(), ref, plant_params=plant_params)
         needs = ctx.needs_input_grad
         grads = any(needs[i] for i in (3, 7, 8, 9))
         g = bank_loss_vjp(bank_loop, r["x"], r["u"], ref, pl.rows(), pl.p_scale, u_prev,
                           tuple(t.detach() for t in (w_inp, b_inp, w_out)), plant_params, pl.truncate, want_x0=needs[3],
-                          value_only=not grads)
+                          value_only=not grads, process_noise=process_noise,
+                          x_state=r["x_state"] if meas_noise is not None else None)
         features.update(cost=g["cost"], x=r["x"], u=r["u"], metrics=r["metrics"])
+        if noisy:
+            features["x_state"] = r["x_state"]
         ctx.grads = grads
         if grads:
             ctx.like = tuple((t.shape, t.device, t.dtype) for t in (x0, w_inp, b_inp, w_out))
@@ -109,7 +123,7 @@ class _PressLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss):
         if not ctx.grads:
-            return (None,) * 10
+            return (None,) * 12
         g_x0, g_wi, g_bi, g_wo = ctx.stash
         gl = g_loss.to(torch.float64)
         like = lambda t, to: t.reshape(to[0]).to(device=to[1], dtype=to[2])
@@ -119,10 +133,10 @@ class _PressLossFn(torch.autograd.Function):
             g_x0 = g_x0 * gl[:, None, None]
             out_x0 = like(g_x0 if len(x0_[0]) == 3 else g_x0.sum(0), x0_)   # a shared x0: the sum over the models
         return (None, None, None, out_x0, None, None, None, like(g_wi * gl[:, None, None], wi_),
-                like(g_bi * gl[:, None], bi_), like(g_wo * gl[:, None], wo_))
+                like(g_bi * gl[:, None], bi_), like(g_wo * gl[:, None], wo_), None, None)
 
 
-def train_on_press(batches, bank_loop, press_loss: PressLoss, optimizer, plant_sampler=None, step=None):
+def train_on_press(batches, bank_loop, press_loss: PressLoss, optimizer, plant_sampler=None, step=None, noise_sampler=None):
     """:func:`~.many.train_models` on the press: for every batch ``(x0, ref)`` or ``(x0, ref, u_prev)`` one training
     step of all the bank's models — the forward launch, the fused reverse launch, ``losses.sum().backward()`` (the
     models are independent: each receives the gradient of its own loss) and ``optimizer.step()``.
@@ -131,7 +145,9 @@ def train_on_press(batches, bank_loop, press_loss: PressLoss, optimizer, plant_s
     ``plant_sampler(B)``: called once per batch, returns that batch's press — a ``(B,28)`` or ``(M,B,28)`` table (domain
     randomisation, for example ``PressParams.sample``), or anything else ``plant_params`` takes; ``None``: the loop's
     own press. ``step(x0, ref, plant_params, u_prev) -> (losses, features)`` replaces the default body of a step
-    (zero_grad, forward, backward, optimizer step). Returns ``(mean loss per model over the batches, {"cost": (M, sum of
+    (zero_grad, forward, backward, optimizer step). ``noise_sampler(B, T)``: called once per batch, returns that batch's
+    ``(process_noise, meas_noise)``, either of which may be ``None`` (for example ``lambda B, T: device_noise(B, T, p_std,
+    m_std, device, generator)``); with it a ``step`` is called with ``process_noise=`` and ``meas_noise=`` as well. Returns ``(mean loss per model over the batches, {"cost": (M, sum of
     the batches' B), "metrics": the last batch's})``."""
     if press_loss.loop is not bank_loop:
         raise ValueError("train_on_press: press_loss was built on another loop than bank_loop")
@@ -142,11 +158,14 @@ def train_on_press(batches, bank_loop, press_loss: PressLoss, optimizer, plant_s
     for x0, ref, *more in batches:
         u_prev = more[0] if more else None
         plant = None if plant_sampler is None else plant_sampler(x0.shape[-2])
+        noise = {}
+        if noise_sampler is not None:
+            noise["process_noise"], noise["meas_noise"] = noise_sampler(x0.shape[-2], ref.shape[-1])
         if step is not None:
-            losses, f = step(x0, ref, plant, u_prev)
+            losses, f = step(x0, ref, plant, u_prev, **noise)
         else:
             optimizer.zero_grad()
-            losses, f = press_loss.forward(x0, ref, plant_params=plant, u_prev=u_prev)
+            losses, f = press_loss.forward(x0, ref, plant_params=plant, u_prev=u_prev, **noise)
             losses.sum().backward()
             optimizer.step()
         losses = losses.detach()

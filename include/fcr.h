@@ -571,6 +571,38 @@ int fcr_closed_loop_bank_loss_vjp(const fcr_closed_loop_bank_grad *args, const f
                                   size_t ws_bytes, void *stream);
 
 /*
+ * Training on the press under pre-drawn process and measurement noise (a pure addition to ABI 8). The
+ * forward is fcr_closed_loop_run_bank's loop: the controller reads the RECORD m_t = x[:, t], the press steps the
+ * unperturbed STATE s_t with process_noise[b,t] added to the right-hand side at every RK4 stage, and x[:, t+1] = s_{t+1} +
+ * meas_noise[b,t]. The adjoint seeds on the record (the loss and the metrics are evaluated there; dL/ds = dL/dm, v being
+ * additive), takes the controller chain and its masks from the record, and linearises the plant at (s_t, u_t, w_t). The
+ * noise is a constant: no gradient is produced for it. Feasibility recovery is not covered.
+ *
+ *   fcr_closed_loop_run_bank_press_state: fcr_closed_loop_run_bank_press (press NULL, both strides 0: the reference's
+ *     press, fcr_closed_loop_run_bank) that stores per step (args->x, args->u required) and also writes the states to
+ *     x_state (M,B,T+1,5): x_state[:, :, 0] = x0 and x_state[:, :, t+1] + meas_noise[:, t] == x[:, :, t+1] bit for bit.
+ *     x, u and every statistic are the bits of the call without x_state. args->feasibility must be NULL.
+ *   fcr_bank_noise: what the adjoint reads of the noisy run beside fcr_closed_loop_bank_grad. process_noise: the
+ *     forward's, model m's at process_noise + m * process_stride ELEMENTS (0: one (B,T,5) shared, else >= B*T*5), or NULL
+ *     (none was drawn). x_state: the forward's states, or NULL: there was no measurement noise and the record is the state.
+ *   fcr_closed_loop_bank_vjp_noise / fcr_closed_loop_bank_loss_vjp_noise: fcr_closed_loop_bank_vjp /
+ *     fcr_closed_loop_bank_loss_vjp on such a run: the same arguments, outputs, workspace, conventions, truncation and
+ *     empty cases (n_models = 0, B = 0, T = 0); with zero-filled noise they compute what those compute.
+ */
+typedef struct fcr_bank_noise {
+    const double *process_noise;
+    int64_t process_stride;
+    const double *x_state;
+} fcr_bank_noise;
+
+int fcr_closed_loop_run_bank_press_state(const fcr_closed_loop_bank *args, const double *press, int64_t stride_model,
+                                         int64_t stride_traj, const fcr_press *model, double *x_state, void *stream);
+int fcr_closed_loop_bank_vjp_noise(const fcr_closed_loop_bank_grad *args, const fcr_bank_noise *noise, const double *g_x,
+                                   const double *g_u, void *ws, size_t ws_bytes, void *stream);
+int fcr_closed_loop_bank_loss_vjp_noise(const fcr_closed_loop_bank_grad *args, const fcr_bank_noise *noise,
+                                        const fcr_press_loss *loss, void *ws, size_t ws_bytes, void *stream);
+
+/*
  * The model-predictive baseline on the press (a pure addition to ABI 8): a shooting MPC with the
  * reference's objective on the RK4 press, one lane per trajectory, all in fp64.
  *
