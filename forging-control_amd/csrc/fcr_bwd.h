@@ -157,6 +157,8 @@ constexpr float kInvNegLog2e = 1.0f / kNegLog2e;
 // NX_OWN: the next cell's is fetched. NX_SAME_PHASE: the next cell is t - 1 of this layer (false: the last cell of a
 // phase that ends before t = 0, fcr_bwd_kernel's reach rule). (The f16 mode's record holds f16(h) only: tanh(c_t) = h f16-rounded / o, the
 // same accuracy against the fp64 oracle as re-evaluating tanh from the c record, scripts/f16_errs.py, and 5 % faster.)
+// DX_ONLY: the last cell of a phase of fcr_bwd_kernel (FIRST, or truncated-last), whose dh_prev and dc go nowhere: only
+// the output tiles that hold a dx slot are formed (dx_tile); dh and dc hold no result on exit (the caller resets them).
 #ifndef FCR_STAMP
 #define FCR_STAMP 0   // diagnostic: per-wave s_memtime sums of the cell's sections (ws tail)
 #endif
@@ -172,7 +174,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 
 template <int HS, bool L0, bool DIN, bool FIRST, bool NX_L0, bool NX_HC, bool NX_DIN, bool LP, bool OWN = true,
-          bool NX_OWN = true, bool DG = false, bool NX_SAME_PHASE = true>
+          bool NX_OWN = true, bool DG = false, bool NX_SAME_PHASE = true, bool DX_ONLY = false>
 __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, const float (&ext)[HS],
                                          float (&dh)[HS], float (&dc)[HS], float (&dxo)[HS], float &dxq,
                                          float &dx4, CellIn<HS> &ci, const NextIn &nx, Stamps &sp,
@@ -191,6 +193,9 @@ __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, con
     constexpr uint32_t LO = I::HALF;                    // lo image
     constexpr int KLO = (L0 && FIRST) ? G::XBLK : 0;
     constexpr int KHI = FIRST ? (L0 ? G::XBLK + 1 : G::KX1) : KB;
+    // output tile tau holds slots 4 tau .. 4 tau + 3 of [dx ; dh_prev] (layer 0: [dh_prev ; dxq ; dx4]); DX_ONLY keeps
+    // the tiles with a dx slot: layer 0's last one, the first ceil(HS / 4) otherwise
+    auto dx_tile = [](int tau) { return !DX_ONLY || (L0 ? 4 * tau + 3 >= HS : 4 * tau < HS); };
 
     float up, down, sg0, sgg;   // the trajectory's power-of-two scale, set once the incoming dh is in
     float dgd = 0.0f;           // DG: down, or 0 when the trajectory has no gradient here (its dgates are zero)
@@ -256,7 +261,7 @@ __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, con
         else lstm_point_grad<FIRST>(a, cpv, P, Q);
         // torch LSTM semantics: dc = dc_carried + dh dh/dc; the carried dc of the cell below is dc f
         const float dcv = fmaf(dh[r], P[0], dc[r]);
-        dc[r] = dcv * Q[1];
+        if (!DX_ONLY) dc[r] = dcv * Q[1];
         const float dcs = dcv * sg0;
         va[0] = va[1] = dcs;
         va[2] = dcv * sgg;
@@ -366,6 +371,7 @@ __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, con
         if (kbb + 2 < KBB) fwd_pair(kbb + 2, fa[(kbb + 2) % 3]);
 #pragma unroll
         for (int tau = 0; tau < NB; ++tau) {
+            if (!dx_tile(tau)) continue;
             const uint32_t ct = 8u * (2 * (tau >> 1) + (tau & 1)) + 2 * kbb * TILE;
             // the last tile of a packed-tail layer: its hi-image rows hold W_hi AND W_lo of the two real
             // inputs (fcr_img.h), so the lo image is not read and its W_lo·dgate_hi product is not issued
@@ -427,19 +433,21 @@ __device__ __forceinline__ void bwd_cell(uint32_t fb, uint32_t tb, int lane, con
     sched_fence();
     const unsigned long long t2 = stamp_now();
     if (L0) {
+        if (!DX_ONLY) {
 #pragma unroll
-        for (int s = 0; s < HS; ++s) dh[s] = acc[s >> 2][s & 3] * down;
+            for (int s = 0; s < HS; ++s) dh[s] = acc[s >> 2][s & 3] * down;
+        }
         dxq = acc[HS >> 2][HS & 3] * down;
         dx4 = acc[(HS + 1) >> 2][(HS + 1) & 3] * down;
     } else {
-        if (TAILT) {   // the last tile's padding rows 2HS, 2HS+1 carry the W_lo terms of rows 2HS-2, 2HS-1
+        if (TAILT && dx_tile(NB - 1)) {   // the last tile's padding rows 2HS, 2HS+1 carry the W_lo terms of rows 2HS-2, 2HS-1
             acc[NB - 1][0] += acc[NB - 1][2];
             acc[NB - 1][1] += acc[NB - 1][3];
         }
 #pragma unroll
         for (int s = 0; s < HS; ++s) {
             dxo[s] = acc[s >> 2][s & 3] * down;
-            dh[s] = acc[(HS + s) >> 2][(HS + s) & 3] * down;
+            if (!DX_ONLY) dh[s] = acc[(HS + s) >> 2][(HS + s) & 3] * down;
         }
     }
     if (FCR_STAMP) {
@@ -687,6 +695,9 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         // the layer below (or of layer 2 of the previous window). t_lo >= 1: the phase ends with a truncated-last cell,
         // not FIRST (it recomputes from h, c of t_lo - 1; its dh_prev, dc go nowhere) with the FIRST cell's prefetch
         // flags and its next cell's own record from the slab (NX_SAME_PHASE = false).
+        // Either way the phase's last cell forms a dh_prev and a dc nothing consumes (dh = dc = 0 opens the next phase):
+        // it runs DX_ONLY. (fp32 mode; the f16 mode's cells are as they were.)
+        constexpr bool DXO = !LP;
         const int t_lo = t_lo_of(j);
         const int t_gen = t_lo > 0 ? t_lo + 1 : 2;   // the generic cells run down to here
         const bool one_cell = t_lo == kL - 1;        // window 0: every phase is its truncated-last cell alone
@@ -697,7 +708,7 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         };
         // t = 9: h_9 of layer 2 only fed the readout (no split record), so this cell re-evaluates tanh(c_9)
         if (one_cell) {
-            bwd_cell<HS, false, false, false, false, true, true, LP, false, true, false, false>(
+            bwd_cell<HS, false, false, false, false, true, true, LP, false, true, false, false, DXO>(
                 L1.fb, L1.tb, lane, dh_out, dh, dc, dxo, unused0, unused1, ci, next_of(j, 2, kL - 1), sp);
         } else {
             bwd_cell<HS, false, false, false, false, true, false, LP, false>(L1.fb, L1.tb, lane, dh_out, dh, dc, dxo, unused0,
@@ -716,11 +727,11 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
             bwd_cell<HS, false, false, false, false, false, false, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
                                                                  unused1, ci, next_of(j, 2, 1), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 1)) * 16), dxo, lane);
-            bwd_cell<HS, false, false, true, false, true, true, LP>(L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0,
-                                                              unused1, ci, next_of(j, 2, 0), sp);
+            bwd_cell<HS, false, false, true, false, true, true, LP, true, true, false, true, DXO>(
+                L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 2, 0), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, 0)) * 16), dxo, lane);
         } else if (!one_cell) {
-            bwd_cell<HS, false, false, false, false, true, true, LP, true, true, false, false>(
+            bwd_cell<HS, false, false, false, false, true, true, LP, true, true, false, false, DXO>(
                 L1.fb, L1.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 2, t_lo), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 2, t_lo)) * 16), dxo, lane);
         }
@@ -741,11 +752,11 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
             bwd_cell<HS, false, true, false, false, false, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
                                                                unused1, ci, next_of(j, 1, 1), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 1)) * 16), dxo, lane);
-            bwd_cell<HS, false, true, true, true, true, true, LP>(L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0,
-                                                            unused1, ci, next_of(j, 1, 0), sp);
+            bwd_cell<HS, false, true, true, true, true, true, LP, true, true, false, true, DXO>(
+                L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 1, 0), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, 0)) * 16), dxo, lane);
         } else {
-            bwd_cell<HS, false, true, false, true, true, true, LP, true, true, false, false>(
+            bwd_cell<HS, false, true, false, true, true, true, LP, true, true, false, false, DXO>(
                 L1b.fb, L1b.tb, lane, dab, dh, dc, dxo, unused0, unused1, ci, next_of(j, 1, t_lo), sp);
             din_store<HS, LP>(nb.rd, (uint32_t)((doff(j, 1, t_lo)) * 16), dxo, lane);
             if (one_cell) din_again(1);
@@ -764,7 +775,7 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
         }
         if (t_lo > 0) {
             float dxq, dx4;
-            bwd_cell<HS, true, true, false, false, true, false, LP, true, false, false, false>(
+            bwd_cell<HS, true, true, false, false, true, false, LP, true, false, false, false, DXO>(
                 L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci, next_of(j, 0, t_lo), sp);
             buf_st2(rr, lane * 8, (uint32_t)((j * kL + t_lo) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row 9
         } else {
@@ -772,8 +783,8 @@ __global__ __launch_bounds__(kBwdWaves * kWave, kBwdWaves / 4) void fcr_bwd_kern
             bwd_cell<HS, true, true, false, true, false, true, LP>(L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci,
                                                              next_of(j, 0, 1), sp);
             buf_st2(rr, lane * 8, (uint32_t)((j * kL + 1) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row j+1
-            bwd_cell<HS, true, true, true, false, true, false, LP, true, false>(L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq,
-                                                                           dx4, ci, next_of(j, 0, 0), sp);
+            bwd_cell<HS, true, true, true, false, true, false, LP, true, false, false, true, DXO>(
+                L0.fb, L0.tb, lane, dab, dh, dc, dxo, dxq, dx4, ci, next_of(j, 0, 0), sp);
             buf_st2(rr, lane * 8, (uint32_t)((j * kL) * kWave * 8), f32x2{dxq * scq, dx4 * sc4});   // row j
         }
     }
