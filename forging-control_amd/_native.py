@@ -43,7 +43,7 @@ EXPORTS = ("fcr_workspace_size", "fcr_wide_kept_windows", "fcr_forward", "fcr_ba
            "fcr_press_grad_sum_workspace_size", "fcr_press_grad_sum", "fcr_closed_loop_bank_vjp_workspace_size",
            "fcr_closed_loop_bank_vjp", "fcr_closed_loop_bank_loss_vjp", "fcr_mpc_workspace_size", "fcr_mpc_solve",
            "fcr_mpc_closed_loop", "fcr_closed_loop_run_bank_press_state", "fcr_closed_loop_bank_vjp_noise",
-           "fcr_closed_loop_bank_loss_vjp_noise")
+           "fcr_closed_loop_bank_loss_vjp_noise", "fcr_lstm_rollout_backward_workspace_size", "fcr_lstm_rollout_backward")
 LOSS_L1, LOSS_MSE = 0, 1
 P1_MAX, P2_MAX = 2.122366, 1.036233   # the default upper pressure bounds (Functions.py:1411; csrc/fcr_common.h)
 
@@ -250,6 +250,14 @@ class FcrSupervised(ctypes.Structure):
     ]
 
 
+class FcrLstmRolloutGrads(ctypes.Structure):
+    """fcr_lstm_rollout_grads (include/fcr.h): where fcr_lstm_rollout_backward writes; g_window0 / g_cmd may be NULL."""
+    _fields_ = [
+        ("g_w_ih", ctypes.c_void_p * 3), ("g_w_hh", ctypes.c_void_p * 3), ("g_fc_w", ctypes.c_void_p),
+        ("g_fc_b", ctypes.c_void_p), ("g_window0", ctypes.c_void_p), ("g_cmd", ctypes.c_void_p),
+    ]
+
+
 _vp, _i32, _i64, _sz, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
 _P = ctypes.POINTER
 _dims, _po, _wts, _pt, _feas, _press = _P(FcrDims), _P(FcrOptions), _P(FcrWeights), _P(FcrLossTerms), _P(FcrFeasibility), _P(FcrPress)
@@ -265,6 +273,9 @@ _SIGNATURES = (
     ("fcr_lstm_backward", _i32, [_dims, _wts, _vp, _P(_vp), _P(_vp), _vp, _vp, _vp, _vp, _sz, _vp]),
     ("fcr_lstm_rollout_workspace_size", _i32, [_dims, _P(_sz)]),
     ("fcr_lstm_rollout", _i32, [_dims, _wts, _vp, _vp, _P(ctypes.c_float), _vp, _vp, _vp, _sz, _vp]),
+    ("fcr_lstm_rollout_backward_workspace_size", _i32, [_dims, _P(_sz)]),                # pure additions to ABI 8
+    ("fcr_lstm_rollout_backward", _i32, [_dims, _wts, _vp, _vp, _P(ctypes.c_float), _vp, _vp, _P(FcrLstmRolloutGrads), _vp,
+                                         _sz, _vp]),
     ("fcr_closed_loop_run", _i32, [_P(FcrClosedLoop), _vp]),
     ("fcr_closed_loop_run_bank", _i32, [_P(FcrClosedLoopBank), _vp]),            # a pure addition to ABI 8
     ("fcr_feasibility_project", _i32, [_feas, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -476,6 +476,37 @@ int fcr_lstm_rollout(const fcr_dims *d, const fcr_weights *w, const float *windo
     return lro_forward(d, w, window0, cmd, gain, noise, xhat, (char *)ws, (hipStream_t)stream);
 }
 
+static int check_lro_bwd_dims(const fcr_dims *d) {
+    if (const int rc = check_lro_dims(d)) return rc;
+    if (!lro_bwd_fits(d)) return fail(FCR_EINVAL, "B*N too large: the backward runs N x (B rounded up to 16) windows, 2^30 at the most");
+    return FCR_OK;
+}
+
+int fcr_lstm_rollout_backward_workspace_size(const fcr_dims *dims, size_t *bytes) {
+    int rc = check_lro_bwd_dims(dims);
+    if (rc) return rc;
+    if (!bytes) return fail(FCR_EINVAL, "bytes is NULL");
+    *bytes = lro_bwd_workspace(dims);
+    return FCR_OK;
+}
+
+int fcr_lstm_rollout_backward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd,
+                              const float *gain, const float *xhat, const float *g_xhat,
+                              const fcr_lstm_rollout_grads *out, void *ws, size_t ws_bytes, void *stream) {
+    int rc = check_lro_bwd_dims(d);
+    if (rc) return rc;
+    if (d->B == 0) return FCR_OK;
+    if (!window0 || !cmd || !xhat || !g_xhat || !out || !ws)
+        return fail(FCR_EINVAL, "fcr_lstm_rollout_backward: a required pointer is NULL");
+    for (int l = 0; l < kLayers; ++l)
+        if (!out->g_w_ih[l] || !out->g_w_hh[l])
+            return fail(FCR_EINVAL, "fcr_lstm_rollout_backward: gradient of layer %d is NULL", l);
+    if (!out->g_fc_w || !out->g_fc_b) return fail(FCR_EINVAL, "fcr_lstm_rollout_backward: a readout gradient is NULL");
+    if (!lstm_weights_ok(w)) return fail(FCR_EINVAL, "fcr_lstm_rollout_backward: an LSTM/fc weight pointer is NULL");
+    if ((rc = check_ws("fcr_lstm_rollout_backward", ws, ws_bytes, lro_bwd_workspace(d)))) return rc;
+    return lro_backward(d, w, window0, cmd, gain, xhat, g_xhat, out, (char *)ws, (hipStream_t)stream);
+}
+
 int fcr_fnn_workspace_size(int32_t B, int32_t hidden, size_t *bytes) {
     if (B < 0 || hidden < 1 || hidden > fnn::kFnnMaxHidden)
         return fail(FCR_EINVAL, "fcr_fnn_workspace_size: B=%d, hidden=%d (1..%d)", B, hidden, fnn::kFnnMaxHidden);

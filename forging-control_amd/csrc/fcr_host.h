@@ -2,7 +2,8 @@
 // of one family and the host code that launches them:
 //   fcr_abi.hip      the C ABI (include/fcr.h): argument checks, process defaults, the controller (fcr_fnn.h)
 //   fcr_rollout.hip  the H <= 52 rollout (fused, small-batch, pipelined kernels), the H <= 52 surrogate step
-//                    (fcr_sur.h) and the kernels every engine shares (fcr_shared_kernels.h)
+//                    (fcr_sur.h), the backward of its free run (fcr_lro_bwd.h) and the kernels every engine shares
+//                    (fcr_shared_kernels.h)
 //   fcr_wide.hip     the H > 52 rollout, the H > 52 surrogate step and the fcr_wide_bwd_cell test hook
 //   fcr_rows.hip     plant, closed loop and bank, feasibility projection, window gather, the supervised baseline's epoch
 //   fcr_grad.hip     the press's adjoint: vector-Jacobian products of the plant rollout and the closed loop
@@ -141,5 +142,11 @@ int sur_backward(const fcr_dims *d, const float *dy, float *const *g_w_ih, float
 size_t lro_workspace(const fcr_dims *d);
 int lro_forward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
                 const float *noise, float *xhat, char *base, hipStream_t s);
+
+// backward of lro_forward (fcr_lro_bwd.h); out: the caller's fcr_lstm_rollout_grads
+bool lro_bwd_fits(const fcr_dims *d);   // T x (B rounded up to 16) windows within the surrogate step's index range
+size_t lro_bwd_workspace(const fcr_dims *d);
+int lro_backward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
+                 const float *xhat, const float *g_xhat, const fcr_lstm_rollout_grads *out, char *base, hipStream_t s);
 
 }  // namespace fcr

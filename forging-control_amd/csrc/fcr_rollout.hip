@@ -20,6 +20,7 @@
 #include "fcr_small.h"
 #include "fcr_sur.h"
 #include "fcr_lstm_rollout.h"   // after the others: built from fcr_fwd.h's parts
+#include "fcr_lro_bwd.h"
 
 namespace fcr {
 namespace {
@@ -726,6 +727,16 @@ int sur_wgrad_t(const SurArgs &a, const SurLayout &L, int l, float *part, float 
     return launch_check("sur_wgrad_finish_kernel");
 }
 
+// the weight gradients of the three layers from the dgate slab a backward kernel left
+template <int HS>
+int sur_wgrads_t(const SurArgs &a, const SurLayout &L, float *const *g_w_ih, float *const *g_w_hh, float *part,
+                 hipStream_t s) {
+    int rc;
+    if ((rc = sur_wgrad_t<HS, false>(a, L, 2, part, g_w_ih[2], g_w_hh[2], s))) return rc;
+    if ((rc = sur_wgrad_t<HS, false>(a, L, 1, part, g_w_ih[1], g_w_hh[1], s))) return rc;
+    return sur_wgrad_t<HS, true>(a, L, 0, part, g_w_ih[0], g_w_hh[0], s);
+}
+
 template <int HS>
 int sur_backward_t(const SurArgs &a, const SurLayout &L, float *const *g_w_ih, float *const *g_w_hh, float *part,
                    hipStream_t s) {
@@ -733,11 +744,20 @@ int sur_backward_t(const SurArgs &a, const SurLayout &L, float *const *g_w_ih, f
     static std::atomic<unsigned long long> attr_done{0};
     if (const int rc = lds_attr((const void *)sur_bwd_kernel<HS>, lds, attr_done, "sur_bwd")) return rc;
     hipLaunchKernelGGL((sur_bwd_kernel<HS>), dim3(L.nw_pad / kBwdWaves), dim3(kBwdWaves * kWave), lds, s, a);
-    int rc = launch_check("sur_bwd_kernel");
+    const int rc = launch_check("sur_bwd_kernel");
     if (rc) return rc;
-    if ((rc = sur_wgrad_t<HS, false>(a, L, 2, part, g_w_ih[2], g_w_hh[2], s))) return rc;
-    if ((rc = sur_wgrad_t<HS, false>(a, L, 1, part, g_w_ih[1], g_w_hh[1], s))) return rc;
-    return sur_wgrad_t<HS, true>(a, L, 0, part, g_w_ih[0], g_w_hh[0], s);
+    return sur_wgrads_t<HS>(a, L, g_w_ih, g_w_hh, part, s);
+}
+
+// readout: d fc.W = dy^T h_9, d fc.b = sum dy (per-tile partials in the weight-gradient scratch, fixed-order sum)
+int sur_readout_grads(const fcr_dims *d, const float *dy, const float *htop, float *part, float *g_fc_w, float *g_fc_b,
+                      hipStream_t s) {
+    const int nfb = (d->B + kFcRows - 1) / kFcRows;
+    hipLaunchKernelGGL(sur_fc_partial_kernel, dim3(nfb), dim3(256), 0, s, dy, htop, d->B, d->H, part);
+    if (const int rc = launch_check("sur_fc_partial_kernel")) return rc;
+    hipLaunchKernelGGL(sur_fc_final_kernel, dim3(kOut * d->H + kOut), dim3(256), 0, s, (const float *)part, nfb, d->H, g_fc_w,
+                       g_fc_b);
+    return launch_check("sur_fc_final_kernel");
 }
 
 }  // namespace
@@ -777,13 +797,24 @@ int sur_backward(const fcr_dims *d, const float *dy, float *const *g_w_ih, float
         default: rc = sur_backward_t<13>(a, L, g_w_ih, g_w_hh, part, s);
     }
     if (rc) return rc;
-    // readout: d fc.W = dy^T h_9, d fc.b = sum dy (per-tile partials in the weight-gradient scratch, fixed-order sum)
-    const int nfb = (d->B + kFcRows - 1) / kFcRows;
-    hipLaunchKernelGGL(sur_fc_partial_kernel, dim3(nfb), dim3(256), 0, s, dy, (const float *)a.htop, d->B, d->H, part);
-    if ((rc = launch_check("sur_fc_partial_kernel"))) return rc;
-    hipLaunchKernelGGL(sur_fc_final_kernel, dim3(kOut * d->H + kOut), dim3(256), 0, s, (const float *)part, nfb, d->H, g_fc_w,
-                       g_fc_b);
-    return launch_check("sur_fc_final_kernel");
+    return sur_readout_grads(d, dy, a.htop, part, g_fc_w, g_fc_b, s);
+}
+
+static void sur_slabs(const fcr_dims *d, char *base, SurArgs *a) { *a = sur_args(d, make_sur(d, 1), base); }
+
+static int sur_grads_of_dgates(const fcr_dims *d, const float *dy, float *const *g_w_ih, float *const *g_w_hh, float *g_fc_w,
+                        float *g_fc_b, char *base, hipStream_t s) {
+    const SurLayout L = make_sur(d, 1);
+    const SurArgs a = sur_args(d, L, base);
+    float *part = (float *)(base + L.part);
+    int rc;
+    switch (L.HS) {
+        case 4: rc = sur_wgrads_t<4>(a, L, g_w_ih, g_w_hh, part, s); break;
+        case 8: rc = sur_wgrads_t<8>(a, L, g_w_ih, g_w_hh, part, s); break;
+        default: rc = sur_wgrads_t<13>(a, L, g_w_ih, g_w_hh, part, s);
+    }
+    if (rc) return rc;
+    return sur_readout_grads(d, dy, a.htop, part, g_fc_w, g_fc_b, s);
 }
 
 namespace {
@@ -856,6 +887,113 @@ int lro_forward(const fcr_dims *d, const fcr_weights *w, const float *window0, c
         case 8: return launch_lro_t<8>(a, L, s);
         default: return launch_lro_t<13>(a, L, s);
     }
+}
+
+}  // namespace fcr
+
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the command-driven surrogate rollout (fcr_lro_bwd.h): the kernels that lay the rollout's windows out as a
+// virtual batch and run the reverse over it, strung together with the surrogate step's forward and weight-gradient
+// kernels above.
+// Workspace: sur_workspace at B' = T*Bp (Bp = B rounded up to 16), then the virtual batch (B',10,5), the recomputed
+// outputs (B',4, unused), ybar (B',4) and the rows P [Bp/16][T+10][64] of 8 bytes, each slab 256-byte aligned.
+// Launches per call, whatever T: lro_windows, the forward's range guard (1, or 2 above 409 windows), pack_all, sur_fwd,
+// lro_bwd, per layer sur_wgrad + sur_part_sum + sur_wgrad_finish, sur_fc_partial, sur_fc_final: 16 or 17.
+namespace fcr {
+namespace {
+
+struct LroBwdLayout {
+    fcr_dims dv;   // the virtual batch's dims: B = T·Bp
+    int nwb;       // waves per step
+    size_t xwin, yrec, ybar, rows, total;
+};
+LroBwdLayout make_lro_bwd(const fcr_dims *d) {
+    LroBwdLayout L{};
+    L.nwb = (d->B + kTile - 1) / kTile;
+    L.dv = *d;
+    L.dv.B = d->N * L.nwb * kTile;
+    L.dv.N = 1;
+    Arena take;
+    take.off = sur_workspace(&L.dv, 1);
+    const size_t Bv = (size_t)L.dv.B;
+    L.xwin = take(sizeof(float) * Bv * kL * kIn);
+    L.yrec = take(sizeof(float) * Bv * kOut);
+    L.ybar = take(sizeof(float) * Bv * kOut);
+    L.rows = take(sizeof(f32x2) * (size_t)L.nwb * (d->N + kL) * kWave);
+    L.total = take.off;
+    return L;
+}
+
+template <int HS>
+int launch_lro_bwd_t(LroBwdArgs &a, hipStream_t s) {
+    using SG = SurGeo<HS>;
+    a.dg_bytes = SG::DG;
+    a.dsc_floats = SG::DSC;
+    const size_t items = (size_t)a.s.B * kL;
+    hipLaunchKernelGGL(lro_windows_kernel, dim3((unsigned)((items + kLroWinBlock - 1) / kLroWinBlock)), dim3(kLroWinBlock), 0,
+                       s, a);
+    return launch_check("lro_windows_kernel");
+}
+template <int HS>
+int launch_lro_cells_t(const LroBwdArgs &a, hipStream_t s) {
+    constexpr int lds = SurGeo<HS>::LDS_BWD;
+    static std::atomic<unsigned long long> attr_done{0};
+    if (const int rc = lds_attr((const void *)lro_bwd_kernel<HS>, lds, attr_done, "lro_bwd")) return rc;
+    hipLaunchKernelGGL((lro_bwd_kernel<HS>), dim3((a.nwb + kBwdWaves - 1) / kBwdWaves), dim3(kBwdWaves * kWave), lds, s, a);
+    return launch_check("lro_bwd_kernel");
+}
+
+}  // namespace
+
+bool lro_bwd_fits(const fcr_dims *d) {   // the virtual batch within the surrogate step's index range
+    const long long nwb = (d->B + kTile - 1) / kTile;
+    return (long long)d->N * nwb * kTile <= (1LL << 30);
+}
+
+size_t lro_bwd_workspace(const fcr_dims *d) { return make_lro_bwd(d).total; }
+
+int lro_backward(const fcr_dims *d, const fcr_weights *w, const float *window0, const float *cmd, const float *gain,
+                 const float *xhat, const float *g_xhat, const fcr_lstm_rollout_grads *out, char *base, hipStream_t s) {
+    const LroBwdLayout L = make_lro_bwd(d);
+    const int HS = slot_tier(d->H);
+    LroBwdArgs a{};
+    sur_slabs(&L.dv, base, &a.s);
+    a.B = d->B;
+    a.T = d->N;
+    a.nwb = L.nwb;
+    a.window0 = window0;
+    a.cmd = cmd;
+    a.xhat = xhat;
+    a.g_xhat = g_xhat;
+    a.g0 = gain ? gain[0] : 1.0f;
+    a.g1 = gain ? gain[1] : 1.0f;
+    a.g2 = gain ? gain[2] : 1.0f;
+    a.g3 = gain ? gain[3] : 1.0f;
+    a.xwin = (float *)(base + L.xwin);
+    a.ybar = (float *)(base + L.ybar);
+    a.rows = (f32x2 *)(base + L.rows);
+    a.g_window0 = out->g_window0;
+    a.g_cmd = out->g_cmd;
+    // the weight-gradient product reads whole groups of kSurKW waves: the one past the last step's is zeroed
+    a.zw0 = d->N * L.nwb;
+    a.zw1 = (a.zw0 + kSurKW - 1) / kSurKW * kSurKW;
+    int rc;
+    switch (HS) {
+        case 4: rc = launch_lro_bwd_t<4>(a, s); break;
+        case 8: rc = launch_lro_bwd_t<8>(a, s); break;
+        default: rc = launch_lro_bwd_t<13>(a, s);
+    }
+    if (rc) return rc;
+    // the stored forward over the virtual batch (its own range guard and packs; the outputs are not used)
+    if ((rc = sur_forward(&L.dv, w, a.xwin, (float *)(base + L.yrec), 1, base, s))) return rc;
+    switch (HS) {
+        case 4: rc = launch_lro_cells_t<4>(a, s); break;
+        case 8: rc = launch_lro_cells_t<8>(a, s); break;
+        default: rc = launch_lro_cells_t<13>(a, s);
+    }
+    if (rc) return rc;
+    return sur_grads_of_dgates(&L.dv, a.ybar, out->g_w_ih, out->g_w_hh, out->g_fc_w, out->g_fc_b, base, s);
 }
 
 }  // namespace fcr

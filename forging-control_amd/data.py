@@ -125,3 +125,45 @@ class DeviceLoader:
             order = order[perm]
         for s in range(0, order.numel(), self.batch_size):
             yield self.w.gather(order[s:s + self.batch_size], check=self.check, preview=self.preview)
+
+
+def free_run_batches(Z, traj_len: int, horizon: int, batch_size: int, Y=None, lookback: int = 10, shuffle: bool = False,
+                     generator: torch.Generator | None = None):
+    """Batches ``(window0 (B,lookback,5), cmd (B,T), target (B,T,4))`` for :func:`~.surrogate.train_free_run`, T = horizon.
+
+    ``Z`` (rows,5) holds ``[y_dot,p1,p2,z,u]`` in the surrogate's input units, trajectories of ``traj_len`` rows one after
+    the other; ``Y`` (rows,4) the states in its output units (default ``Z[:, :4]``). A sample is a start row i of a
+    trajectory, 0 <= i <= traj_len - 1 - T:
+    ``window0[j] = Z[max(i - lookback + 1 + j, 0)]`` (``fcr_window_gather``'s left padding), ``cmd[t] = Z[i + t, 4]``,
+    ``target[t] = Y[i + 1 + t]`` (rows of the sample's trajectory). Tensors are used where they are (torch indexing on
+    their device); samples come in index order, or in a fresh permutation per call when shuffling."""
+    Z = torch.as_tensor(Z)
+    Y = Z[:, :4] if Y is None else torch.as_tensor(Y).to(Z.device)
+    if Z.dim() != 2 or Z.shape[1] != 5 or Y.dim() != 2 or Y.shape[1] != 4 or Y.shape[0] != Z.shape[0]:
+        raise ValueError(f"Z must be (rows, 5) and Y (rows, 4), got {tuple(Z.shape)} and {tuple(Y.shape)}")
+    traj_len, T, lookback, batch_size = int(traj_len), int(horizon), int(lookback), int(batch_size)
+    rows = Z.shape[0]
+    if traj_len < 1 or rows % traj_len:
+        raise ValueError(f"rows={rows} must be a positive multiple of traj_len={traj_len}")
+    if T < 1 or batch_size < 1 or lookback < 1:
+        raise ValueError(f"horizon={T}, batch_size={batch_size} and lookback={lookback} must be >= 1")
+    per = traj_len - T   # start rows of a trajectory
+    if per < 1:
+        raise ValueError(f"horizon={T} leaves no sample in trajectories of {traj_len} rows (needs traj_len >= horizon + 1)")
+    dev = Z.device
+    n = (rows // traj_len) * per
+    order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
+    order = order.to(dev)
+    back = torch.arange(lookback, device=dev) - (lookback - 1)
+    ahead = torch.arange(T, device=dev)
+
+    def batches():
+        for s in range(0, n, batch_size):
+            g = order[s:s + batch_size]
+            k, i = g // per, g % per
+            base = (k * traj_len).unsqueeze(1)
+            wrows = base + (i.unsqueeze(1) + back).clamp_min(0)
+            arows = base + i.unsqueeze(1) + ahead
+            yield Z[wrows], Z[:, 4][arows], Y[arows + 1]
+
+    return batches()

@@ -737,6 +737,28 @@ int fcr_lstm_rollout(const fcr_dims *dims, const fcr_weights *w, const float *wi
                      const float *gain, const float *noise, float *xhat, void *ws, size_t ws_bytes, void *stream);
 
 /*
+ * Backward of fcr_lstm_rollout: training the surrogate on its free run. Given xhat (B,T,4), the predictions the
+ * forward returned for the same window0 / cmd / gain / weights (they already contain the noise, which is therefore not
+ * passed), and g_xhat (B,T,4) = dL/dxhat, it writes the gradient of every LSTM weight and the readout (OVERWRITTEN,
+ * shapes as fcr_lstm_backward, summed over (step, trajectory, cell) in a fixed order: two calls give the same bits) and,
+ * where asked for, of window0 and cmd. g_window0[:,9,4] is exactly 0: that entry is overwritten by cmd[:,0], which
+ * receives its share. noise and gain receive no gradient. `dims` as for fcr_lstm_rollout (N = T >= 1; H <= 52 and
+ * FCR_PRECISION_FP32 only, FCR_EUNSUPPORTED otherwise). The windows of all T steps are rebuilt from xhat and recomputed
+ * with every cell's state kept, so the workspace grows with T (fcr_lstm_rollout_backward_workspace_size); the number of
+ * launches does not. Stream-ordered, no allocation, no host synchronisation. B = 0 is a no-op.
+ */
+typedef struct fcr_lstm_rollout_grads {
+    float *g_w_ih[3], *g_w_hh[3], *g_fc_w, *g_fc_b; /* OVERWRITTEN, shapes as fcr_lstm_backward */
+    float *g_window0;                               /* (B,10,5) or NULL */
+    float *g_cmd;                                   /* (B,T) or NULL */
+} fcr_lstm_rollout_grads;
+int fcr_lstm_rollout_backward_workspace_size(const fcr_dims *dims, size_t *bytes);
+int fcr_lstm_rollout_backward(const fcr_dims *dims, const fcr_weights *w, const float *window0, const float *cmd,
+                              const float *gain /* host float[4] or NULL */, const float *xhat /* (B,T,4), the forward's */,
+                              const float *g_xhat /* (B,T,4) */, const fcr_lstm_rollout_grads *out,
+                              void *ws, size_t ws_bytes, void *stream);
+
+/*
  * Process-wide DEFAULTS of the per-call options (a field set to FCR_OPT_INHERIT takes them).
  * Small batches (fp32-accurate mode, H 17..52): B <= max_batch runs the small-batch kernels, which split each
  * 16-trajectory group's cell over the four waves of a workgroup (the reference trains at B = 15, UL/Main.py:84,297);
